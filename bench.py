@@ -14,13 +14,19 @@ launch  : ``python bench.py --gpus N`` spawns its N ranks itself (torch.distribu
 roofline: the operator application inside the PCG loop of the timed region, measured live with HIP events on the solve stream.
           achieved = ALGORITHMIC bytes per application / average duration; ``achieved_physical`` counts the
           bytes the layout really moves.
-N = 1 adds the sub-records the scene does not cover:
+--full  : a plain run (the command above) measures the headline only: set-up, W warm-up steps, K timed steps, the result line.
+          With --full, N = 1 also adds the sub-records the scene does not cover:
           cloud_1m          : configs[2] (synthetic 1M-point oriented cloud, detail_level=1.0, ONE field) with its operator roofline,
                               and the same workload through the assembled solve -> ``spmv_csr_roofline`` (north_star's SpMV KPI:
                               SURVEY.md section 8d, 8 nnz + 12 M + 4 bytes per launch, target 0.70 of 8 TB/s)
           small_inputs      : configs[0] / configs[1] latencies on the GPU (10 000-point bunny scan sequence, 3 000-point ShapeNet recipe)
           cpu_baseline      : the reference's examples/recons_waymo_cpu.py call sequence on assets/bunny.ply on the host cores
                               (oracle port, oracle/waymo_cpu.py), the GPU on the same input beside it
+          and, beside them, the adaptive mesher timed against the lattice one (``config.mesh_adaptive``) and the live counter passes
+          of ``roofline.traffic``.  The ``--no-*`` options drop single parts of a --full run.
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned to its caller, the stitched mesh, as
+          DIR/*.npy (float32 / float64, a fixed seeded sample of its rows, about 50 MB; see ``dump_outputs``).  The inputs depend on
+          the arguments only, so two builds can be compared output for output.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -200,6 +206,39 @@ def mesh_adaptive_record(field, mise_iter, repeats=2):
     return out
 
 
+# ---- --dump-outputs: what the timed path returned to its caller ---------------------------------------------------------
+DUMP_VERTEX_ROWS = 1 << 21      # x 3 float32 = 25.2 MB
+DUMP_FACE_ROWS = 1 << 20        # x 3 float64 = 25.2 MB
+
+
+def _sample_rows(n, k, seed):
+    """All n row indices when n <= k, else a fixed seeded sample of k of them, in row order."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(path, mesh):
+    """The mesh one step returns, as path/mesh_vertices.npy (float32 [k, 3] positions), path/mesh_faces.npy (float64 [k, 3] vertex
+    indices of k triangles, exact) and path/mesh_counts.npy (float64 [vertices, triangles]).  Meshes of more rows than
+    DUMP_VERTEX_ROWS / DUMP_FACE_ROWS are sampled with fixed seeds, so that the same mesh always gives the same files.
+    Returns {file name: bytes written}."""
+    os.makedirs(path, exist_ok=True)
+    v, f = mesh.v, mesh.f
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    iv = torch.from_numpy(_sample_rows(nv, DUMP_VERTEX_ROWS, 1)).to(v.device)
+    jf = torch.from_numpy(_sample_rows(nf, DUMP_FACE_ROWS, 2)).to(f.device)
+    arrays = {'mesh_vertices': v[iv].to(torch.float32).cpu().numpy(),
+              'mesh_faces': f[jf].cpu().numpy().astype(np.float64),
+              'mesh_counts': np.array([nv, nf], dtype=np.float64)}
+    written = {}
+    for name, a in arrays.items():
+        fn = os.path.join(path, name + '.npy')
+        np.save(fn, np.ascontiguousarray(a))
+        written[name + '.npy'] = os.path.getsize(fn)
+    return written
+
+
 # ---- configs[4]: the scaling scene ------------------------------------------------------------------------------------
 def terrain_setup(rec, dev, n_total, rank, world):
     """Sharded input of the 10M-point scene: the tiles of this rank's chunks and of their neighbours.  The chunk ->
@@ -284,10 +323,18 @@ def main():
     ap.add_argument('--cloud-steps', type=int, default=3)
     ap.add_argument('--dist-probe', action='store_true', help='launch check only: start the N ranks, run the handshake collectives over the '
                                                               'backend, print the ``dist`` record and exit (no reconstruction)')
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline: cloud_1m (+ spmv_csr_roofline), small_inputs, '
+                                                        'cpu_baseline, mesh_adaptive, the live counter passes of roofline.traffic (off: set-up, warm-up, '
+                                                        'the timed steps and the result line only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps write the mesh of the last timed step to DIR/*.npy '
+                                                                       '(rank 0; a fixed seeded sample of its rows, about 50 MB)')
     args = ap.parse_args()
 
     if args.gpus < 1:
         print('bench.py: --gpus must be >= 1', file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print('bench.py: --steps must be >= 1 and --warmup >= 0', file=sys.stderr)
         return 2
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus, sys.argv[1:], probe=args.dist_probe)
@@ -397,7 +444,10 @@ def main():
 
         acc = {}
         dt, (field, mesh), prof, alloc = timed_loop(step, steps, warmup, acc)
-        adaptive = mesh_adaptive_record(field, args.mise_iter) if (world == 1 and not args.no_adaptive) else None
+        if args.dump_outputs and rank == 0:
+            written = dump_outputs(args.dump_outputs, mesh)
+            print('bench.py: wrote %s to %s (%.1f MB)' % (', '.join(sorted(written)), args.dump_outputs, sum(written.values()) / 1e6), file=sys.stderr)
+        adaptive = mesh_adaptive_record(field, args.mise_iter) if (args.full and world == 1 and not args.no_adaptive) else None
         infos = field.chunk_infos()
         cfg = {'workload': 'configs[4]: synthetic %d-point km-scale terrain + boxes (8x8 tiles of 125 m), tree_depth=5, chunk_size=125 m '
                            '(64 chunks), reconstruct(chunk_size=)+extract_dual_mesh(mise_iter=%d), the same scene at every N (strong scaling)' % (n_scene, args.mise_iter),
@@ -468,7 +518,7 @@ def main():
         per = [None] * world
         dist.all_gather_object(per, mine)
         out['dist']['per_rank'] = per
-    if world == 1 and not args.no_cloud:
+    if args.full and world == 1 and not args.no_cloud:
         torch.cuda.empty_cache()
         cdt, cn, ccfg, cprof, cstages, calloc, extra = run_cloud(args.cloud_steps, 1, True)
         cloud = {'value': cn * args.cloud_steps / cdt, 'unit': 'points/s', 'ms_per_step': cdt / args.cloud_steps * 1e3, 'steps': args.cloud_steps, 'warmup': 1,
@@ -486,9 +536,9 @@ def main():
         out['cloud_1m'] = cloud
     else:
         extra = None
-    if world == 1 and not args.no_small_inputs:
+    if args.full and world == 1 and not args.no_small_inputs:
         out['small_inputs'] = small_inputs(dev)
-    if rank == 0 and world == 1 and not args.no_live_pmc and not os.environ.get('NKSR_BENCH_CHILD') and out.get('roofline'):
+    if args.full and rank == 0 and world == 1 and not args.no_live_pmc and not os.environ.get('NKSR_BENCH_CHILD') and out.get('roofline'):
         # same-run counter figure for roofline.traffic (the committed record of profiles/ stays the fallback)
         torch.cuda.empty_cache()
         tb, per_kernel, note = live_traffic_fused(['--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--no-cloud', '--no-small-inputs', '--no-live-pmc',
@@ -501,7 +551,7 @@ def main():
             out['roofline'].pop('traffic_note', None)
         elif note:
             out['roofline']['traffic_live_note'] = note
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(dev, args, extra)
     elif rank == 0:
         out['cpu_baseline'] = None

@@ -157,3 +157,39 @@ def test_committed_bench_line_and_its_pmc_records():
             model = r['physical_bytes_per_launch']
             assert 0.85 * model <= r['traffic'] <= 1.20 * model, (name, r['traffic'], model)
     assert line['ms_per_step'] < 420.0 and 'device_allocs_per_step' in line['allocator']
+
+
+def test_dump_outputs_writes_float_arrays_of_a_fixed_sample(tmp_path):
+    """--dump-outputs: the mesh a step returns as float .npy files, every row when it is small, a fixed seeded sample of rows (in row
+    order) when it is large, the same files for the same mesh, 64 MB at most whatever its size."""
+    import types
+    import torch
+    b = _bench()
+    rs = np.random.default_rng(3)
+    v = torch.from_numpy(rs.random((5000, 3), dtype=np.float32))
+    f = torch.from_numpy(rs.integers(0, 5000, (9000, 3)).astype(np.int32))
+    mesh = types.SimpleNamespace(v=v, f=f)
+    w = b.dump_outputs(str(tmp_path / 'all'), mesh)
+    assert sorted(w) == ['mesh_counts.npy', 'mesh_faces.npy', 'mesh_vertices.npy']
+    lv, lf, lc = (np.load(str(tmp_path / 'all' / n)) for n in ('mesh_vertices.npy', 'mesh_faces.npy', 'mesh_counts.npy'))
+    assert lv.dtype == np.float32 and lf.dtype == np.float64 and lc.dtype == np.float64
+    assert np.array_equal(lv, v.numpy()) and np.array_equal(lf, f.numpy()) and lc.tolist() == [5000, 9000]
+    b.DUMP_VERTEX_ROWS, b.DUMP_FACE_ROWS = 1000, 700
+    for d in ('s1', 's2'):
+        b.dump_outputs(str(tmp_path / d), mesh)
+    sv, sf = np.load(str(tmp_path / 's1' / 'mesh_vertices.npy')), np.load(str(tmp_path / 's1' / 'mesh_faces.npy'))
+    assert sv.shape == (1000, 3) and sf.shape == (700, 3)
+    iv, jf = b._sample_rows(5000, 1000, 1), b._sample_rows(9000, 700, 2)
+    assert np.all(np.diff(iv) > 0) and np.array_equal(sv, v.numpy()[iv]) and np.array_equal(sf, f.numpy()[jf])
+    for n in ('mesh_vertices.npy', 'mesh_faces.npy', 'mesh_counts.npy'):
+        assert open(str(tmp_path / 's1' / n), 'rb').read() == open(str(tmp_path / 's2' / n), 'rb').read()
+    full = _bench()
+    assert full.DUMP_VERTEX_ROWS * 3 * 4 + full.DUMP_FACE_ROWS * 3 * 8 + 1024 <= 64 * 2 ** 20
+
+
+def test_plain_run_options():
+    """``--full`` (the sub-records) and ``--dump-outputs DIR`` exist; --steps sets the timed steps and must be at least one."""
+    r = _run_bench(['--help'], timeout=120)
+    assert r.returncode == 0 and '--full' in r.stdout and '--dump-outputs' in r.stdout
+    r = _run_bench(['--gpus', '1', '--steps', '0', '--warmup', '0'], timeout=120)
+    assert r.returncode == 2 and '--steps must be >= 1' in r.stderr

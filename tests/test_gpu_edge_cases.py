@@ -117,13 +117,13 @@ def test_grid_upsample_and_max_points_batches():
 
 
 def test_bench_contract_line():
-    """bench.py prints ONE JSON line with the driver's keys + roofline + cpu_baseline."""
+    """bench.py --full prints ONE JSON line with the driver's keys + roofline + the sub-records + cpu_baseline."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '1', '--warmup', '1',
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '1', '--warmup', '1', '--full',
                           '--points', '60000', '--cpu-sample', '1500', '--scene-points', '640000', '--cpu-cores', '2', '--cpu-repeats', '1'],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -167,6 +167,40 @@ def test_bench_contract_line():
     assert c['kind'] == 'port' and c['cores'] == 2 and c['value'] > 0 and 'recons_waymo_cpu.py' in c['sample']
     assert c['gpu_same_input']['value'] > 0 and c['gpu_same_input']['ms'] > 0 and c['workload_crop']['value'] > 0
     assert d['small_inputs']['configs1_shapenet_3k']['ms'] > 0
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_the_same_mesh(tmp_path):
+    """A plain ``bench.py`` run is the headline and nothing else: exactly --steps timed steps (value = points / ms_per_step), no
+    sub-records, no live counter passes.  --dump-outputs writes the mesh of the last timed step as float .npy files within 64 MB,
+    and two runs with other step counts write the same files (same inputs, deterministic path)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = {}
+    for steps, warmup in ((2, 0), (1, 1)):
+        d_out = str(tmp_path / ('s%d' % steps))
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup),
+                              '--scene-points', '640000', '--dump-outputs', d_out], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d['steps'] == steps and d['warmup'] == warmup and d['ms_per_step'] > 0 and d['dtype'] == 'f32'
+        assert abs(d['value'] * d['ms_per_step'] * 1e-3 - d['config']['scene_points']) < 1e-6 * d['config']['scene_points']
+        assert d['roofline']['launches_timed'] > 0 and not (d['roofline']['traffic_source'] or '').startswith('live')
+        assert d['cpu_baseline'] is None and 'mesh_adaptive' not in d['config']
+        assert not {'cloud_1m', 'spmv_csr_roofline', 'small_inputs'} & set(d)
+        files = sorted(os.listdir(d_out))
+        assert files == ['mesh_counts.npy', 'mesh_faces.npy', 'mesh_vertices.npy']
+        assert sum(os.path.getsize(os.path.join(d_out, f)) for f in files) <= 64 * 2 ** 20
+        arrays = {f: np.load(os.path.join(d_out, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays['mesh_counts.npy'].tolist() == [d['config']['mesh_vertices'], d['config']['mesh_triangles']]
+        got[steps] = arrays
+    for f in got[2]:
+        np.testing.assert_array_equal(got[2][f], got[1][f])
 
 
 def test_reconstruct_is_bitwise_deterministic():
