@@ -169,9 +169,9 @@ __device__ __forceinline__ void asm_lm_mfma(const AsmLanePtr<NT>& P, int r0, int
         for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v[n], acc[n], 0, 0, 0);
     }
 }
-// lane pointers of level d's column tiles for the rows r_lo .. of ONE level-d cell (dense rows: they do not depend on the cell)
+// lane pointers of level d's column tiles (they do not depend on the cell)
 template <int NT>
-__device__ __forceinline__ void asm_lm_pointers(const AsmArgs& A, int d, int r_lo, int lane, AsmLanePtr<NT>& P) {
+__device__ __forceinline__ void asm_lm_pointers(const AsmArgs& A, int d, int lane, AsmLanePtr<NT>& P) {
     const nksr_siteset_t& S = A.sets[0];
     const int L = A.hier.depth;
     const int T = (L - d) * 27;
@@ -185,26 +185,6 @@ __device__ __forceinline__ void asm_lm_pointers(const AsmArgs& A, int d, int r_l
         // (columns past T are never used but their loads are unconditional: they read level d -- the array may START at level
         // S.level_base, KernelField.assemble, and the launch's levels are >= it)
         P.p[n] = (col == T && S.target) ? S.target : S.val + (col < T ? (int64_t)(d + dd - S.level_base) * S.level_stride * 27 + sl : (int64_t)(d - S.level_base) * S.level_stride * 27);
-        if (S.compact_nbr32 && !(col == T && S.target)) {
-            // COMPACT rows (csrc/fused.hip, k_fz_row_sizes): the rows r_lo .. r_hi of this cell lie in ONE cell of every coarser level too;
-            // that cell's block holds, per row, the slots of its existing neighbours.  A column whose neighbour does not exist (or past
-            // T) reads the zero word of the array at stride 0.
-            P.mul[n] = 0;
-            P.p[n] = S.val;
-            if (col < T) {
-                const int cj = S.compact_cells[(int64_t)(d + dd) * S.level_stride + r_lo];
-                if (cj >= 0) {
-                    const int32_t* tb = S.compact_nbr32 + (int64_t)cj * 32;
-                    const unsigned m = (unsigned)tb[31];
-                    if ((m >> sl) & 1u) {
-                        const int k = __popc(m);
-                        P.mul[n] = k;
-                        // (indexed by the ABSOLUTE row below: the pointer is taken back by the cell's first row)
-                        P.p[n] = S.val + ((int64_t)tb[30] * 4 + __popc(m & ((1u << sl) - 1u)) - (int64_t)tb[28] * k);
-                    }
-                }
-            }
-        }
     }
 }
 template <int NT>
@@ -213,7 +193,7 @@ __device__ __forceinline__ void asm_accumulate_lm(const AsmArgs& A, int d, int r
     const nksr_siteset_t& S = A.sets[0];
     const int j = lane & 31, half = lane >> 5;
     AsmLanePtr<NT> P;
-    asm_lm_pointers<NT>(A, d, r_lo, lane, P);
+    asm_lm_pointers<NT>(A, d, lane, P);
     const float w = S.weight;
     float bA[ASM_TRIP][NT], bB[ASM_TRIP][NT];
     asm_lm_load<NT>(P, r_lo, r_lo, r_hi, half, bA);
@@ -799,8 +779,8 @@ extern "C" int nksr_assemble(const nksr_hier_t* h, const nksr_siteset_t* sets, i
     for (int si = 0; si < nsets; ++si) {
         total_rows += sets[si].n * sets[si].ncomp;
         if (si > 0 && (sets[si].level_stride != 0) != lm) return nksr_set_error(NKSR_ERR_ARG, "site sets mix site-major and level-major rows");
-        if (sets[si].level_base < 0 || sets[si].level_base >= h->depth || (sets[si].level_base > 0 && (!sets[si].level_stride || sets[si].compact_nbr32)))
-            return nksr_set_error(NKSR_ERR_ARG, "site set: level_base needs dense level-major rows and a level of the hierarchy");
+        if (sets[si].level_base < 0 || sets[si].level_base >= h->depth || (sets[si].level_base > 0 && !sets[si].level_stride))
+            return nksr_set_error(NKSR_ERR_ARG, "site set: level_base needs level-major rows and a level of the hierarchy");
         lm = sets[si].level_stride != 0;
         for (int d = 0; d < sets[si].level_base; ++d)
             if (h->lv[d].n > 0) return nksr_set_error(NKSR_ERR_ARG, "site set: rows start at level %d but level %d of the hierarchy has cells", (int)sets[si].level_base, d);

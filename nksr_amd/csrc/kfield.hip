@@ -5,7 +5,6 @@
 // trilinear stencil and 27 psi gathers through the neighbour table; the interpolator MLP
 // weights live in LDS.
 #include "kfield_dev.h"
-#include <stdlib.h>
 
 // ---- psi_j = feat_j + MLP(feat_j) -----------------------------------------------------------
 template <int K, int H>
@@ -39,8 +38,9 @@ __device__ __forceinline__ void store_row27(float* __restrict__ p, const float v
 template <int K, int H, bool GRAD, bool JAC>
 __global__ void __launch_bounds__(128) k_kernel_rows(nksr_hier_t hier, const float* __restrict__ xyz, int64_t n, float row_scale_,
                               const float* __restrict__ site_scale, int64_t level_stride, const int32_t* __restrict__ row_index, int32_t* __restrict__ row_cells,
-                              float* __restrict__ val, float* __restrict__ dval, uint32_t level_map) {
-    const int d = (level_map >> (4 * blockIdx.y)) & 15, L = hier.depth;
+                              float* __restrict__ val, float* __restrict__ dval) {
+    const unsigned d = blockIdx.y;                            // (unsigned: its 64-bit products need no sign extension)
+    const int L = hier.depth;
     const nksr_level_t& lv = hier.lv[d];
     __shared__ float w[MlpView<K, H>::SIZE];
     for (int i = threadIdx.x; i < MlpView<K, H>::SIZE; i += blockDim.x) w[i] = lv.mlp[i];
@@ -186,20 +186,6 @@ extern "C" int nksr_voxel_psi(const float* feat, int32_t n, int kdim, int hidden
     return NKSR_OK;
 }
 
-// NKSR_ROWS_LEVELS (probe, tools/rows_probe.py): only these levels ("0,2"); the rows of the others stay unwritten
-uint32_t nksr_rows_level_map(int depth, int* nlev) {
-    uint32_t level_map = 0;
-    int n = 0;
-    const char* e = getenv("NKSR_ROWS_LEVELS");
-    if (e && *e) {
-        for (const char* p = e; *p; ++p)
-            if (*p >= '0' && *p <= '9' && (*p - '0') < depth) level_map |= (uint32_t)(*p - '0') << (4 * n++);
-    } else {
-        for (int d = 0; d < depth; ++d) level_map |= (uint32_t)d << (4 * n++);
-    }
-    *nlev = n;
-    return level_map;
-}
 extern "C" int nksr_kernel_rows(const nksr_hier_t* h, const float* xyz, int64_t n, int approx, float row_scale, const float* site_scale,
                                 int64_t level_stride, const int32_t* row_index, int32_t* row_cells, float* val, float* dval, void* stream) {
     if (n <= 0) return NKSR_OK;
@@ -207,13 +193,11 @@ extern "C" int nksr_kernel_rows(const nksr_hier_t* h, const float* xyz, int64_t 
     if ((row_index || row_cells) && (level_stride <= 0 || (val && dval)))
         return nksr_set_error(NKSR_ERR_ARG, "row_index / row_cells need the level-major layout and ONE kind of rows (val or dval)");
     if (h->depth < 1 || h->depth > NKSR_MAX_DEPTH) return nksr_set_error(NKSR_ERR_ARG, "bad depth %d", h->depth);
-    int nlev = 0;
-    const uint32_t level_map = nksr_rows_level_map(h->depth, &nlev);
-    dim3 grid(nksr_blocks(n, 128), nlev), block(128);
+    dim3 grid(nksr_blocks(n, 128), h->depth), block(128);
     DISPATCH_KH(h->kdim, h->hidden, {
-        if (!dval) hipLaunchKernelGGL((k_kernel_rows<K, H, false, false>), grid, block, 0, (hipStream_t)stream, *h, xyz, n, row_scale, site_scale, level_stride, row_index, row_cells, val, dval, level_map);
-        else if (approx) hipLaunchKernelGGL((k_kernel_rows<K, H, true, false>), grid, block, 0, (hipStream_t)stream, *h, xyz, n, row_scale, site_scale, level_stride, row_index, row_cells, val, dval, level_map);
-        else hipLaunchKernelGGL((k_kernel_rows<K, H, true, true>), grid, block, 0, (hipStream_t)stream, *h, xyz, n, row_scale, site_scale, level_stride, row_index, row_cells, val, dval, level_map);
+        if (!dval) hipLaunchKernelGGL((k_kernel_rows<K, H, false, false>), grid, block, 0, (hipStream_t)stream, *h, xyz, n, row_scale, site_scale, level_stride, row_index, row_cells, val, dval);
+        else if (approx) hipLaunchKernelGGL((k_kernel_rows<K, H, true, false>), grid, block, 0, (hipStream_t)stream, *h, xyz, n, row_scale, site_scale, level_stride, row_index, row_cells, val, dval);
+        else hipLaunchKernelGGL((k_kernel_rows<K, H, true, true>), grid, block, 0, (hipStream_t)stream, *h, xyz, n, row_scale, site_scale, level_stride, row_index, row_cells, val, dval);
     })
     NKSR_CHECK_LAUNCH();
     return NKSR_OK;
