@@ -598,6 +598,38 @@ int nksr_mc_emit_pairs(const int32_t* corner_idx, const int32_t* config, const i
 int nksr_pair_vertices(const int64_t* pair_keys, int64_t npair, const int64_t* cell_keys, const int32_t* cell_lam, const float* cell_pos,
                        const float* f, float u, float* verts_out, void* stream);
 
+
+/* ---- mesh metrics (metrics.MeshEvaluator, reference models/nksr_net.py:298-310; nksr_amd/metrics.py) ----------------------------
+ * Faces are [nf, 3] vertex indices, int32 (faces_int64 = 0) or int64 (faces_int64 != 0); a face with an index outside [0, nv) counts
+ * as a face of zero area.  n_points > 0 with zero faces, NULL arrays and negative sizes are argument errors. */
+/* per face: unit normal (fp32, 0 for a zero-area face) and area (fp64, from the fp32 vertices); the CDF of the sampler is the inclusive
+ * fp64 sum of the areas (nksr_inclusive_sum_f64) */
+int nksr_mesh_face_areas(const float* v, int64_t nv, const void* faces, int faces_int64, int64_t nf, float* normal_out, double* area_out,
+                         void* stream);
+/* bitwise-reproducible inclusive fp64 prefix sum (rocPRIM deterministic scan; tmp / tmp_bytes as nksr_exclusive_sum_i32) */
+int nksr_inclusive_sum_f64(void* tmp, size_t* tmp_bytes, const double* in, double* out, int64_t n, void* stream);
+/* n area-uniform samples of the mesh.  Sample i is a pure function of (seed, i): Philox4x32-10 with key (seed & 0xffffffff, seed >> 32)
+ * and counter (i & 0xffffffff, i >> 32, 0, 0) gives the words r0..r3;
+ *   u0 = ((r0 << 21) ^ (r1 >> 11)) 2^-53 picks the face: the first j with cdf[j] > u0 cdf[nf - 1] (a zero-area face is never picked);
+ *   u1 = r2 2^-32, u2 = r3 2^-32, s = sqrt(u1):  x = (1 - s) a + s (1 - u2) b + s u2 c  (fp64, rounded to fp32 once);
+ * normal_out[i] = face_normal[j], face_out[i] = j.  cdf [nf] from nksr_inclusive_sum_f64 over the areas (total > 0). */
+int nksr_mesh_sample(const float* v, int64_t nv, const void* faces, int faces_int64, int64_t nf, const double* cdf, const float* face_normal,
+                     int64_t n, uint64_t seed, float* xyz_out, float* normal_out, int64_t* face_out, void* stream);
+/* Exact nearest neighbour of every query in the cloud of `pyramid` (k = 1 over the octree of nksr_sdf_from_points_pyramid; a query the
+ * search cannot reach -- far outside the cloud, or outside the key range -- takes a box-pruned pass over the n_top top-level cells, whose
+ * sorted keys are top_keys).  Outputs, each optional (NULL): dist_out [nq] = |q - p_nn|, dot_out [nq] = |n_q . n_nn| of the unit
+ * normals (0 where either normal is zero; needs normal_sorted, in the pyramid's point order, and query_normal), partials_out
+ * [ceil(nq / NKSR_NN_BLOCK), NKSR_METRIC_FIELDS] = per workgroup: sum d, sum d^2, sum dot, then the counts of d <= t for t in
+ * NKSR_METRIC_THRESHOLDS, all fp64, each block summed in a fixed order. */
+#define NKSR_NN_BLOCK 128
+#define NKSR_METRIC_NTHRESH 5
+#define NKSR_METRIC_FIELDS 8
+#define NKSR_METRIC_THRESHOLDS {0.01, 0.015, 0.02, 0.002, 0.1}
+int nksr_nn_metrics(const nksr_knn_pyramid_t* pyramid, const int64_t* top_keys, int32_t n_top, const float* normal_sorted, const float* query,
+                    const float* query_normal, int64_t nq, int max_ring, float* dist_out, float* dot_out, double* partials_out, void* stream);
+/* out [NKSR_METRIC_FIELDS] = the column sums of partials [nrows, NKSR_METRIC_FIELDS], one workgroup, fixed order (no atomics) */
+int nksr_metric_reduce(const double* partials, int64_t nrows, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,8 @@ import sys
 
 import nksr_amd
 from nksr_amd import *  # noqa: F401,F403
-from nksr_amd import configs, fields, svh, utils  # noqa: F401
+from nksr_amd import configs, fields, metrics, svh, utils  # noqa: F401
 
-for _name in ('configs', 'fields', 'svh', 'utils'):
+for _name in ('configs', 'fields', 'metrics', 'svh', 'utils'):
     sys.modules['nksr.' + _name] = getattr(nksr_amd, _name)
 __version__ = nksr_amd.__version__

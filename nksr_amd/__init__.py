@@ -5,12 +5,12 @@ use: ``Reconstructor``, ``NKSRNetwork``, ``SparseFeatureH
 ``get_estimate_normal_preprocess_fn`` and the sub-modules ``fields``, ``svh``, ``configs``,
 ``utils``.  ``import nksr`` resolves to this package through the top-level ``nksr`` shim.
 """
-from . import configs, fields, svh, utils
+from . import configs, fields, metrics, svh, utils
 from .nn.network import NKSRNetwork
 from .preprocess import get_estimate_normal_preprocess_fn
 from .reconstructor import Reconstructor
 from .svh import SparseFeatureHierarchy
 
 __all__ = ['Reconstructor', 'NKSRNetwork', 'SparseFeatureHierarchy', 'get_estimate_normal_preprocess_fn',
-           'fields', 'svh', 'configs', 'utils']
+           'fields', 'svh', 'configs', 'utils', 'metrics']
 __version__ = '0.1.0'

@@ -36,6 +36,9 @@ class KnnPyramidT(C.Structure):
                 ('levels', _i32), ('leaf', _i32), ('cell', _f32), ('inv_cell', _f32)]
 
 
+NN_BLOCK = 128            # NKSR_NN_BLOCK: queries per workgroup of nksr_nn_metrics (one partials row each)
+METRIC_FIELDS = 8         # NKSR_METRIC_FIELDS: sum d, sum d^2, sum dot, five threshold counts
+
 CELL_SIZES = 12
 
 
@@ -207,6 +210,11 @@ _PROTOS = {
     'nksr_adaptive_positions': [_vp, _vp, _i64, _f32, _vp, _vp],
     'nksr_mc_emit_pairs': [_vp, _vp, _vp, _i64, _vp, _vp],
     'nksr_pair_vertices': [_vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp],
+    'nksr_mesh_face_areas': [_vp, _i64, _vp, C.c_int, _i64, _vp, _vp, _vp],
+    'nksr_inclusive_sum_f64': [_vp, _P(_sz), _vp, _vp, _i64, _vp],
+    'nksr_mesh_sample': [_vp, _i64, _vp, C.c_int, _i64, _vp, _vp, _i64, C.c_uint64, _vp, _vp, _vp, _vp],
+    'nksr_nn_metrics': [_P(KnnPyramidT), _vp, _i32, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp],
+    'nksr_metric_reduce': [_vp, _i64, _vp, _vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(lib, _name)

@@ -765,6 +765,63 @@ struct KnnPyramid {
     float cell, inv_cell;
 };
 #define KNN_PYR_BLOCK 128
+// cell ci = (cx, cy, cz) of level l: scanned when it is a leaf, else descended (children nearest octant first, every child whose box
+// lies farther than the current k-th candidate cut off) down to leaves of <= P.leaf points
+template <int KMAX>
+__device__ __forceinline__ void knn_descend(const KnnPyramid& P, int l, int ci, int cx, int cy, int cz, const float q[3], TopK<KMAX>& top,
+                                            int* node, unsigned char* cursor) {
+    int lvl = l;
+    bool enter = true;
+    for (;;) {
+        if (enter) {
+            const int s = P.start[lvl][ci], e = P.end[lvl][ci];
+            if (lvl == 0 || e - s <= P.leaf) {
+                knn_scan<KMAX>(P.xyz, s, e, q, top);
+                if (lvl == l) return;
+                ++lvl; cx >>= 1; cy >>= 1; cz >>= 1;               // back to the parent
+            } else {
+                node[lvl * KNN_PYR_BLOCK] = ci;
+                cursor[lvl * KNN_PYR_BLOCK] = 0;
+            }
+            enter = false;
+            continue;
+        }
+        // the next child of node[lvl] (cell (cx, cy, cz) of level lvl) worth a visit
+        const int nd = node[lvl * KNN_PYR_BLOCK];
+        int t = cursor[lvl * KNN_PYR_BLOCK];
+        const unsigned mask = P.cmask[lvl][nd];
+        const float cl = P.cell * (float)(1 << lvl), ch = 0.5f * cl, slack = 0.02f * ch;
+        const unsigned qo = (q[0] >= ((float)cx + 0.5f) * cl ? 1u : 0u) | (q[1] >= ((float)cy + 0.5f) * cl ? 2u : 0u) |
+                            (q[2] >= ((float)cz + 0.5f) * cl ? 4u : 0u);
+        bool found = false;
+        while (t < 8) {
+            const unsigned o = ((0x76534210u >> (4 * t)) & 7u) ^ qo;      // octants by the number of axes they differ from q's in
+            ++t;
+            if (!((mask >> o) & 1u)) continue;
+            const int x = 2 * cx + (int)(o & 1u), y = 2 * cy + (int)((o >> 1) & 1u), z = 2 * cz + (int)(o >> 2);
+            const float lo[3] = {(float)x * ch, (float)y * ch, (float)z * ch};
+            float gap2 = 0.f;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float e = fmaxf(fmaxf(lo[a] - q[a], q[a] - (lo[a] + ch)) - slack, 0.f);
+                gap2 = fmaf(e, e, gap2);
+            }
+            if (gap2 > top.kth()) continue;
+            ci = P.child[lvl][nd] + __popc(mask & ((1u << o) - 1u));
+            cx = x; cy = y; cz = z;
+            found = true;
+            break;
+        }
+        if (found) {
+            cursor[lvl * KNN_PYR_BLOCK] = (unsigned char)t;
+            --lvl;
+            enter = true;
+        } else {
+            if (lvl == l) return;
+            ++lvl; cx >>= 1; cy >>= 1; cz >>= 1;
+        }
+    }
+}
 template <int KMAX>
 __device__ __forceinline__ bool knn_topk_pyramid(const KnnPyramid& P, const float q[3], int k, int max_ring, TopK<KMAX>& top, int* node,
                                                  unsigned char* cursor) {
@@ -797,59 +854,9 @@ __device__ __forceinline__ bool knn_topk_pyramid(const KnnPyramid& P, const floa
         const float cell_l = P.cell * (float)(1 << l);
         const int c[3] = {c0[0] >> l, c0[1] >> l, c0[2] >> l};
         const int rc = knn_rings<KMAX>(cell_l, q, c, k, max_ring, l + 1 < P.levels, top, [&](int cx, int cy, int cz) {
-            int ci = hash_find(P.hkeys[l], P.hvals[l], P.hcap[l], morton_biased(cx, cy, cz, NKSR_BIAS0 >> l));
+            const int ci = hash_find(P.hkeys[l], P.hvals[l], P.hcap[l], morton_biased(cx, cy, cz, NKSR_BIAS0 >> l));
             if (ci < 0) return;
-            int lvl = l;
-            bool enter = true;
-            for (;;) {
-                if (enter) {
-                    const int s = P.start[lvl][ci], e = P.end[lvl][ci];
-                    if (lvl == 0 || e - s <= P.leaf) {
-                        knn_scan<KMAX>(P.xyz, s, e, q, top);
-                        if (lvl == l) return;
-                        ++lvl; cx >>= 1; cy >>= 1; cz >>= 1;               // back to the parent
-                    } else {
-                        node[lvl * KNN_PYR_BLOCK] = ci;
-                        cursor[lvl * KNN_PYR_BLOCK] = 0;
-                    }
-                    enter = false;
-                    continue;
-                }
-                // the next child of node[lvl] (cell (cx, cy, cz) of level lvl) worth a visit
-                const int nd = node[lvl * KNN_PYR_BLOCK];
-                int t = cursor[lvl * KNN_PYR_BLOCK];
-                const unsigned mask = P.cmask[lvl][nd];
-                const float cl = P.cell * (float)(1 << lvl), ch = 0.5f * cl, slack = 0.02f * ch;
-                const unsigned qo = (q[0] >= ((float)cx + 0.5f) * cl ? 1u : 0u) | (q[1] >= ((float)cy + 0.5f) * cl ? 2u : 0u) |
-                                    (q[2] >= ((float)cz + 0.5f) * cl ? 4u : 0u);
-                bool found = false;
-                while (t < 8) {
-                    const unsigned o = ((0x76534210u >> (4 * t)) & 7u) ^ qo;      // octants by the number of axes they differ from q's in
-                    ++t;
-                    if (!((mask >> o) & 1u)) continue;
-                    const int x = 2 * cx + (int)(o & 1u), y = 2 * cy + (int)((o >> 1) & 1u), z = 2 * cz + (int)(o >> 2);
-                    const float lo[3] = {(float)x * ch, (float)y * ch, (float)z * ch};
-                    float gap2 = 0.f;
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        const float e = fmaxf(fmaxf(lo[a] - q[a], q[a] - (lo[a] + ch)) - slack, 0.f);
-                        gap2 = fmaf(e, e, gap2);
-                    }
-                    if (gap2 > top.kth()) continue;
-                    ci = P.child[lvl][nd] + __popc(mask & ((1u << o) - 1u));
-                    cx = x; cy = y; cz = z;
-                    found = true;
-                    break;
-                }
-                if (found) {
-                    cursor[lvl * KNN_PYR_BLOCK] = (unsigned char)t;
-                    --lvl;
-                    enter = true;
-                } else {
-                    if (lvl == l) return;
-                    ++lvl; cx >>= 1; cy >>= 1; cz >>= 1;
-                }
-            }
+            knn_descend<KMAX>(P, l, ci, cx, cy, cz, q, top, node, cursor);
         });
         if (rc == 1) return true;
     }
@@ -1058,6 +1065,118 @@ extern "C" int nksr_knn_mean_dist(const float* xyz_sorted, int64_t n, const int3
     else if (k <= 16) hipLaunchKernelGGL((k_knn_mean_dist_topk<16>), gr, bl, 0, (hipStream_t)stream, g, n, k, max_ring, out, valid_out);
     else if (k <= 32) hipLaunchKernelGGL((k_knn_mean_dist_topk<32>), gr, bl, 0, (hipStream_t)stream, g, n, k, max_ring, out, valid_out);
     else hipLaunchKernelGGL(k_knn_mean_dist, gr, bl, 0, (hipStream_t)stream, g, n, k, max_ring, out, valid_out);
+    NKSR_CHECK_LAUNCH();
+    return NKSR_OK;
+}
+
+// ---- exact 1-NN of every query with the mesh-metric epilogue (nksr_amd/metrics.py) ----------------------------------------------------
+// Every query gets its nearest point.  The pyramid search (k = 1) answers the queries it can reach; a query it cannot -- farther from
+// the cloud than max_ring rings of the top level, or with a cell index outside the biased 21-bit key range -- takes the box-pruned pass
+// over ALL top-level cells instead: the cell of the nearest box first, then every cell whose box is not farther than the best
+// candidate so far, each descended like any other.  The top level has a handful of cells (PointPyramid stops at <= 8).
+template <int KMAX>
+__device__ __forceinline__ void knn_topk_all(const KnnPyramid& P, const int64_t* __restrict__ top_keys, int n_top, const float q[3], int k,
+                                             TopK<KMAX>& top, int* node, unsigned char* cursor) {
+    top.init(k);
+    const int l = P.levels - 1;
+    const float cl = P.cell * (float)(1 << l), slack = 0.02f * cl;
+    auto gap = [&](int t, int c[3]) {
+        morton_decode_biased(top_keys[t], NKSR_BIAS0 >> l, c[0], c[1], c[2]);
+        float g2 = 0.f;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float lo = (float)c[a] * cl;
+            const float e = fmaxf(fmaxf(lo - q[a], q[a] - (lo + cl)) - slack, 0.f);
+            g2 = fmaf(e, e, g2);
+        }
+        return g2;
+    };
+    int best = -1, c[3];
+    float bg = 3.4e38f;
+    for (int t = 0; t < n_top; ++t) {
+        const float g2 = gap(t, c);
+        if (g2 < bg) { bg = g2; best = t; }
+    }
+    if (best < 0) return;
+    gap(best, c);
+    knn_descend<KMAX>(P, l, best, c[0], c[1], c[2], q, top, node, cursor);
+    for (int t = 0; t < n_top; ++t) {
+        if (t == best || gap(t, c) > top.kth()) continue;
+        knn_descend<KMAX>(P, l, t, c[0], c[1], c[2], q, top, node, cursor);
+    }
+}
+// One thread per query: dist = |q - p_nn| (fp64 from the fp32 coordinates), dot = |n_q . n_nn| of the two normals scaled to unit length
+// (a zero normal gives 0).  Per workgroup, fp64 sums of d, d^2, dot and the counts of d <= t for the five thresholds, reduced over the
+// block in a fixed tree order: the partials (and nksr_metric_reduce over them) are bitwise reproducible.
+__global__ void __launch_bounds__(NKSR_NN_BLOCK) k_nn_metrics(KnnPyramid Parg, const int64_t* __restrict__ top_keys, int n_top,
+                                                              const float* __restrict__ tnrm, const float* __restrict__ query,
+                                                              const float* __restrict__ qnrm, int64_t nq, int max_ring, float* __restrict__ dist,
+                                                              float* __restrict__ dot, double* __restrict__ partials) {
+    static_assert(NKSR_NN_BLOCK == KNN_PYR_BLOCK, "one LDS slot row per thread");
+    __shared__ int s_node[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
+    __shared__ unsigned char s_cursor[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
+    __shared__ KnnPyramid P;
+    __shared__ double s_red[NKSR_METRIC_FIELDS][NKSR_NN_BLOCK];
+    if (threadIdx.x == 0) P = Parg;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * NKSR_NN_BLOCK + threadIdx.x;
+    double acc[NKSR_METRIC_FIELDS];
+#pragma unroll
+    for (int f = 0; f < NKSR_METRIC_FIELDS; ++f) acc[f] = 0.0;
+    if (i < nq) {
+        const float q[3] = {query[i * 3], query[i * 3 + 1], query[i * 3 + 2]};
+        int* node = &s_node[0][threadIdx.x];
+        unsigned char* cursor = &s_cursor[0][threadIdx.x];
+        TopK<1> top;
+        const float lim = (float)(NKSR_BIAS0 >> 1);           // cell indices well inside the biased key range
+        const bool in_range = fabsf(q[0] * P.inv_cell) < lim && fabsf(q[1] * P.inv_cell) < lim && fabsf(q[2] * P.inv_cell) < lim;
+        if (!in_range || !knn_topk_pyramid<1>(P, q, 1, max_ring, top, node, cursor))
+            knn_topk_all<1>(P, top_keys, n_top, q, 1, top, node, cursor);
+        const int j = top.idx[0];
+        double d = __builtin_nan(""), dt = 0.0;
+        if (j >= 0) {
+            const double ex = (double)q[0] - (double)P.xyz[j * 3], ey = (double)q[1] - (double)P.xyz[j * 3 + 1],
+                         ez = (double)q[2] - (double)P.xyz[j * 3 + 2];
+            d = sqrt(ex * ex + ey * ey + ez * ez);
+            if (tnrm && qnrm) {
+                const double ax = qnrm[i * 3], ay = qnrm[i * 3 + 1], az = qnrm[i * 3 + 2];
+                const double bx = tnrm[j * 3], by = tnrm[j * 3 + 1], bz = tnrm[j * 3 + 2];
+                const double la = fmax(sqrt(ax * ax + ay * ay + az * az), 1e-30), lb = fmax(sqrt(bx * bx + by * by + bz * bz), 1e-30);
+                dt = fabs(ax * bx + ay * by + az * bz) / (la * lb);
+            }
+        }
+        if (dist) dist[i] = (float)d;
+        if (dot) dot[i] = (float)dt;
+        const double th[NKSR_METRIC_NTHRESH] = NKSR_METRIC_THRESHOLDS;
+        acc[0] = d; acc[1] = d * d; acc[2] = dt;
+#pragma unroll
+        for (int t = 0; t < NKSR_METRIC_NTHRESH; ++t) acc[3 + t] = d <= th[t] ? 1.0 : 0.0;
+    }
+    if (!partials) return;
+#pragma unroll
+    for (int f = 0; f < NKSR_METRIC_FIELDS; ++f) s_red[f][threadIdx.x] = acc[f];
+    __syncthreads();
+    for (int s = NKSR_NN_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+#pragma unroll
+            for (int f = 0; f < NKSR_METRIC_FIELDS; ++f) s_red[f][threadIdx.x] += s_red[f][threadIdx.x + s];
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < NKSR_METRIC_FIELDS) partials[(int64_t)blockIdx.x * NKSR_METRIC_FIELDS + threadIdx.x] = s_red[threadIdx.x][0];
+}
+extern "C" int nksr_nn_metrics(const nksr_knn_pyramid_t* pyramid, const int64_t* top_keys, int32_t n_top, const float* normal_sorted,
+                               const float* query, const float* query_normal, int64_t nq, int max_ring, float* dist_out, float* dot_out,
+                               double* partials_out, void* stream) {
+    if (nq < 0 || n_top < 0) return nksr_set_error(NKSR_ERR_ARG, "nn metrics: negative size (nq=%lld, n_top=%d)", (long long)nq, n_top);
+    if (nq == 0) return NKSR_OK;
+    if (!query || !top_keys || n_top < 1) return nksr_set_error(NKSR_ERR_ARG, "nn metrics: NULL query / top-level keys or an empty target");
+    if (!dist_out && !dot_out && !partials_out) return nksr_set_error(NKSR_ERR_ARG, "nn metrics: no output (dist, dot and partials all NULL)");
+    if (dot_out && (!normal_sorted || !query_normal)) return nksr_set_error(NKSR_ERR_ARG, "nn metrics: dot output needs both normal arrays");
+    if (max_ring < 1) return nksr_set_error(NKSR_ERR_ARG, "nn metrics: max_ring must be >= 1 (got %d)", max_ring);
+    KnnPyramid P;
+    if (int rc = make_pyramid(P, pyramid)) return rc;
+    hipLaunchKernelGGL(k_nn_metrics, dim3(nksr_blocks(nq, NKSR_NN_BLOCK)), dim3(NKSR_NN_BLOCK), 0, (hipStream_t)stream, P, top_keys, (int)n_top,
+                       normal_sorted, query, query_normal, nq, max_ring, dist_out, dot_out, partials_out);
     NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }

@@ -59,3 +59,12 @@ extern "C" int nksr_exclusive_sum_i64(void* tmp, size_t* tmp_bytes, const int64_
     NKSR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, *tmp_bytes, in, out, n, (hipStream_t)stream));
     return NKSR_OK;
 }
+
+// the sampler's area CDF: rocPRIM's deterministic look-back, so the fp64 sums (and with them every sample) repeat bit for bit
+extern "C" int nksr_inclusive_sum_f64(void* tmp, size_t* tmp_bytes, const double* in, double* out, int64_t n, void* stream) {
+    if (!tmp_bytes) return nksr_set_error(NKSR_ERR_ARG, "tmp_bytes is NULL");
+    if (n < 0) return nksr_set_error(NKSR_ERR_ARG, "inclusive sum: negative size");
+    if (tmp && n > 0 && (!in || !out)) return nksr_set_error(NKSR_ERR_ARG, "inclusive sum: NULL arrays");
+    NKSR_CHECK_HIP(rocprim::deterministic_inclusive_scan(tmp, *tmp_bytes, in, out, (size_t)n, rocprim::plus<double>(), (hipStream_t)stream));
+    return NKSR_OK;
+}

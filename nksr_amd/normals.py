@@ -85,6 +85,7 @@ class PointPyramid:
             keys, start, end = up, s2, e2
         t.levels = lvl
         self.levels = lvl
+        self.top_keys = keys                    # sorted keys of the top level (the exhaustive pass of nksr_nn_metrics)
         self.top_cell = pg.cell * (1 << (lvl - 1))
         self.struct = t
 
