@@ -630,6 +630,55 @@ int nksr_nn_metrics(const nksr_knn_pyramid_t* pyramid, const int64_t* top_keys, 
 /* out [NKSR_METRIC_FIELDS] = the column sums of partials [nrows, NKSR_METRIC_FIELDS], one workgroup, fixed order (no atomics) */
 int nksr_metric_reduce(const double* partials, int64_t nrows, double* out, void* stream);
 
+/* ---- mesh queries (nksr_amd/mesh_query.py: MeshQuery, the o3d-iou of metrics.MeshEvaluator; reference metrics.py:182-190) -------
+ * A linear BVH over the triangles (Karras, HPG 2012), built in four steps: nksr_bvh_morton (codes of the face centroids in the box of
+ * the vertices), nksr_sort_pairs_u64_u32 (code, face index), nksr_bvh_nodes, nksr_bvh_refit.  The same input gives the same tree bit
+ * for bit.  Internal node i of F - 1 is NKSR_BVH_NODE_FLOATS floats: the boxes of its two children (lo xyz, hi xyz each: [0, 6) and
+ * [6, 12)), then the children as int32 bits ([12], [13]; c >= 0 an internal node, c < 0 leaf ~c), then two zeros.  Leaf k (sorted
+ * position) is NKSR_BVH_LEAF_FLOATS floats: the fp32 corners a, b, c, then the original face index as int32 bits, then two zeros.
+ * A face with an index outside [0, nv) gets an empty box and NaN corners: it is never crossed and never nearest.  F = 1: the root is
+ * leaf 0.  Queries read `depth` (the host copy of *depth_dev, which the refit writes) and refuse a tree deeper than NKSR_BVH_STACK
+ * (NKSR_ERR_CAPACITY). */
+#define NKSR_BVH_NODE_FLOATS 16
+#define NKSR_BVH_LEAF_FLOATS 12
+#define NKSR_BVH_STACK 64
+#define NKSR_BVH_MAX_FACES (1ll << 30)
+/* ray directions of nksr_mesh_occupancy (rays = 1, 3, 5 or 7 use the first `rays` rows): not axis-aligned, the dominant component of
+ * each exactly +-1, every component a short binary fraction, so the shear of the watertight test is exact */
+#define NKSR_BVH_MAX_RAYS 7
+#define NKSR_BVH_RAY_DIRS {{0.5f, 0.25f, 1.0f}, {1.0f, -0.375f, 0.625f}, {-0.625f, 1.0f, -0.25f}, {-0.25f, -0.5f, -1.0f}, \
+                           {-1.0f, 0.625f, -0.375f}, {0.375f, -1.0f, 0.5f}, {-0.375f, 0.75f, 1.0f}}
+typedef struct {
+    int64_t n_faces;           /* F: leaves; F - 1 internal nodes; 0 <= F <= 2^30 (node indices stay int32)                     */
+    int32_t depth;             /* edges from the root to the deepest leaf (host copy of *depth_dev after the refit)               */
+    int32_t reserved;
+    float* nodes;              /* [max(F - 1, 1), NKSR_BVH_NODE_FLOATS]                                                           */
+    float* leaves;             /* [F, NKSR_BVH_LEAF_FLOATS]                                                                       */
+    const float* box;          /* [6] box of the vertices (lo xyz, hi xyz; nksr_bbox): the Morton frame and the culling pad       */
+    int32_t* depth_dev;        /* [1] written by nksr_bvh_refit                                                                   */
+} nksr_bvh_t;
+/* Morton codes (21 bits per axis, quantised in box6) of the centroids of faces [n, 3] (faces != NULL) or of the points xyz[0, n)
+ * (faces == NULL); index_out[i] = i.  The query kernels take such a sorted order to walk neighbouring queries together. */
+int nksr_bvh_morton(const float* xyz, int64_t nv, const void* faces, int faces_int64, int64_t n, const float* box6, uint64_t* codes_out,
+                    uint32_t* index_out, void* stream);
+/* internal nodes from the sorted codes (equal codes split by their sorted position): child words of bvh->nodes, and parent_work
+ * [2F - 1] = 2 * parent + side (internal nodes first, then the leaves) */
+int nksr_bvh_nodes(const uint64_t* codes_sorted, int32_t* parent_work, const nksr_bvh_t* bvh, void* stream);
+/* leaf records of the faces in `order` (the sorted face indices) and every box, bottom up: the second child to reach a node (integer
+ * atomic flag) writes the node's box into its parent; flag_work [2 (F - 1)] int32 (flags, heights; zeroed here); *depth_dev = depth */
+int nksr_bvh_refit(const float* v, int64_t nv, const void* faces, int faces_int64, const uint32_t* order, const int32_t* parent_work,
+                   int32_t* flag_work, const nksr_bvh_t* bvh, void* stream);
+/* Occupancy by ray parity: from every query, `rays` half-lines along NKSR_BVH_RAY_DIRS; every crossing counts (watertight test of
+ * Woop, Benthin and Wald 2013 with exact signs and a per-edge tie-break).  inside_out[q] = 1 when more than
+ * rays / 2 of the counts are odd; counts_out [nq, rays] int32 (optional).  order: NULL or a permutation of [0, nq) (the walk order;
+ * results land at the query's own index). */
+int nksr_mesh_occupancy(const nksr_bvh_t* bvh, const float* query, int64_t nq, const uint32_t* order, int rays, uint8_t* inside_out,
+                        int32_t* counts_out, void* stream);
+/* Closest point (Ericson's point-triangle routine in fp32): dist_out [nq] (inf with no faces), face_out [nq] original face index (the
+ * smaller one on a tie; -1 with no faces), point_out [nq, 3]; each optional, not all NULL. */
+int nksr_mesh_closest(const nksr_bvh_t* bvh, const float* query, int64_t nq, const uint32_t* order, float* dist_out, int64_t* face_out,
+                      float* point_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

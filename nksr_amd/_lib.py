@@ -39,6 +39,19 @@ class KnnPyramidT(C.Structure):
 NN_BLOCK = 128            # NKSR_NN_BLOCK: queries per workgroup of nksr_nn_metrics (one partials row each)
 METRIC_FIELDS = 8         # NKSR_METRIC_FIELDS: sum d, sum d^2, sum dot, five threshold counts
 
+BVH_NODE_FLOATS = 16      # NKSR_BVH_NODE_FLOATS: two child boxes, two child words, two zeros
+BVH_LEAF_FLOATS = 12      # NKSR_BVH_LEAF_FLOATS: corners a, b, c, face index, two zeros
+BVH_STACK = 64            # NKSR_BVH_STACK: traversal stack entries per lane (deepest tree a query accepts)
+BVH_MAX_FACES = 1 << 30   # NKSR_BVH_MAX_FACES
+BVH_MAX_RAYS = 7          # NKSR_BVH_MAX_RAYS
+BVH_RAY_DIRS = ((0.5, 0.25, 1.0), (1.0, -0.375, 0.625), (-0.625, 1.0, -0.25), (-0.25, -0.5, -1.0), (-1.0, 0.625, -0.375),
+                (0.375, -1.0, 0.5), (-0.375, 0.75, 1.0))      # NKSR_BVH_RAY_DIRS
+
+
+class BvhT(C.Structure):
+    _fields_ = [('n_faces', _i64), ('depth', _i32), ('reserved', _i32), ('nodes', _vp), ('leaves', _vp), ('box', _vp), ('depth_dev', _vp)]
+
+
 CELL_SIZES = 12
 
 
@@ -215,6 +228,11 @@ _PROTOS = {
     'nksr_mesh_sample': [_vp, _i64, _vp, C.c_int, _i64, _vp, _vp, _i64, C.c_uint64, _vp, _vp, _vp, _vp],
     'nksr_nn_metrics': [_P(KnnPyramidT), _vp, _i32, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp],
     'nksr_metric_reduce': [_vp, _i64, _vp, _vp],
+    'nksr_bvh_morton': [_vp, _i64, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp],
+    'nksr_bvh_nodes': [_vp, _vp, _P(BvhT), _vp],
+    'nksr_bvh_refit': [_vp, _i64, _vp, C.c_int, _vp, _vp, _vp, _P(BvhT), _vp],
+    'nksr_mesh_occupancy': [_P(BvhT), _vp, _i64, _vp, C.c_int, _vp, _vp, _vp],
+    'nksr_mesh_closest': [_P(BvhT), _vp, _i64, _vp, _vp, _vp, _vp, _vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(lib, _name)

@@ -9,18 +9,22 @@ Every stage runs on the GPU (csrc/metrics.hip: face areas, the fp64 area CDF, th
 csrc/knn.hip: the exact nearest neighbour of every query over an octree of the other cloud).  Coordinates are recentred in float64
 by the centre of the target's bounding box before they are rounded to float32, so scenes far from the origin keep their precision.
 Results are bitwise reproducible: the samples depend on (seed, index) only and no sum uses float atomics.
-``o3d-iou`` (occupancy of ``onet_samples``) needs ray queries against the mesh and is not provided.
+``o3d-iou`` (requested through ``metric_names``) is the volumetric IoU against ``onet_samples`` = (points, occupancy): the mesh's
+occupancy of the points by ray parity (``MeshQuery``, nksr_amd/mesh_query.py: a BVH over the triangles, csrc/meshquery.hip), then
+sum(pd & gt) / (sum(pd | gt) + 1e-6) with integer counts, as in the reference (metrics.py:182-190).
 """
 import numpy as np
 import torch
 
 from ._lib import METRIC_FIELDS, NN_BLOCK, call, ptr, require_gpu, stream, with_tmp
 from .density import bbox_center
+from .mesh_query import MeshQuery, mesh_occupancy  # noqa: F401  (re-exported: nksr.metrics.MeshQuery)
 from .normals import PointGrid, PointPyramid, choose_cell_size
 
 THRESHOLDS = (0.01, 0.015, 0.02, 0.002, 0.1)    # NKSR_METRIC_THRESHOLDS; 'f-score' at [0], '-15' [1], '-20' [2], '-outdoor' [4]
 MAX_RING = 4                                    # rings per pyramid level before a query climbs (nksr_nn_metrics)
 _KEY_CELLS = float(1 << 18)                     # |coordinate| / cell stays below this: cell indices far inside the 21-bit key range
+IOU_RAYS = 3                                    # rays per ONet sample of 'o3d-iou' (majority of three parities)
 
 
 def _device(device):
@@ -226,9 +230,15 @@ class MeshEvaluator:
 
     def eval_mesh(self, mesh, pointcloud_tgt, normals_tgt, onet_samples=None, seed=0):
         """Metrics of `mesh` (a MeshingResult or anything with .v / .f) against the target cloud: ``n_points`` samples of the
-        surface, scored with ``evaluate``.  A mesh without area scores NaN throughout."""
-        if onet_samples is not None:
-            raise NotImplementedError('o3d-iou (occupancy of onet_samples) needs ray queries against the mesh: not provided')
+        surface, scored with ``evaluate``; with 'o3d-iou' in ``metric_names``, also the IoU of the mesh's occupancy of
+        ``onet_samples`` = (points [N, 3], occupancy [N], nonzero = inside) against theirs.  A mesh without area scores NaN
+        throughout."""
+        want_iou = 'o3d-iou' in self.metric_names
+        if onet_samples is not None and not want_iou:
+            raise NotImplementedError("onet_samples given but 'o3d-iou' is not in metric_names: add 'o3d-iou' to metric_names to "
+                                      "score them")
+        if want_iou and onet_samples is None:
+            raise ValueError("'o3d-iou' needs onet_samples = (points, occupancy)")
         dev = self.device
         centre = _bbox_centre(pointcloud_tgt)
         v32 = _recentre(mesh.v, centre, dev, 'mesh.v')
@@ -240,7 +250,23 @@ class MeshEvaluator:
             return self._nan()
         p, n, _ = sample_from_cdf(v32, ff, fn, cdf, self.n_points, seed)
         t = _recentre(pointcloud_tgt, centre, dev, 'pointcloud_tgt')
-        return self._evaluate(p, n, t, _normals32(normals_tgt, t.shape[0], dev, 'normals_tgt'))
+        out = self._evaluate(p, n, t, _normals32(normals_tgt, t.shape[0], dev, 'normals_tgt'))
+        if want_iou:
+            out['o3d-iou'] = self._iou(MeshQuery.recentred(v32, ff, centre), onet_samples)
+        return out
+
+    def _iou(self, query, onet_samples):
+        """sum(pd & gt) / (sum(pd | gt) + 1e-6), integer counts (the reference's formula, metrics.py:186-188)."""
+        if len(onet_samples) != 2:
+            raise ValueError('onet_samples: expected (points, occupancy)')
+        pts, occ = onet_samples
+        gt = occ.detach() if isinstance(occ, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(occ)))
+        gt = (gt.to(self.device) != 0).reshape(-1)
+        pd = query.occupancy(pts, rays=IOU_RAYS)
+        if gt.shape[0] != pd.shape[0]:
+            raise ValueError('onet_samples: %d occupancy values for %d points' % (gt.shape[0], pd.shape[0]))
+        inter, union = int((pd & gt).sum()), int((pd | gt).sum())
+        return inter / (union + 1.0e-6)
 
     def evaluate(self, pointcloud, pointcloud_tgt, normals=None, normals_tgt=None):
         """The metric dict of a given sample set against the target (the reference's ``_evaluate``)."""
