@@ -34,6 +34,76 @@ def test_struct_layouts_match_the_header():
     assert _lib.lib.nksr_pcg_workspace_bytes(1000, 50000) >= 4 * 4000
 
 
+def _flat(v):
+    return [x for r in v for x in _flat(r)] if isinstance(v, tuple) else [v]
+
+
+def test_bindings_match_what_the_compiler_sees(tmp_path):
+    """The bindings are read from the header by nksr_amd/_cheader.py, so comparing them with the header proves nothing; the second
+    witness is the compiler the library is built with (host only, no device code): sizeof and offsetof of every field of every
+    struct, and the value and kind of every numeric macro."""
+    import keyword
+    import subprocess
+    from nksr_amd import _lib, build
+    src = re.sub(r'/\*.*?\*/', '', open(build.HEADER).read(), flags=re.S)
+    structs = re.findall(r'\}\s*(nksr_\w+_t)\s*;', src)
+    macros = re.findall(r'#define (NKSR_\w+)[ \t]+\S', src)
+    assert len(structs) == 11 and set(structs) == set(_lib._STRUCTS) and len(macros) >= 15
+    lines = ['#include <cstddef>', '#include <cstdio>', '#include <type_traits>', '#include "nksr_hip.h"', 'int main() {']
+    for s in structs:
+        lines.append('  printf("%s . %%zu 0\\n", sizeof(%s));' % (s, s))
+        for f, _ in _lib._STRUCTS[s]._fields_:
+            c = f[:-1] if keyword.iskeyword(f[:-1]) else f             # lambda_ -> lambda
+            lines.append('  printf("%s %s %%zu %%zu\\n", sizeof(((%s*)0)->%s), offsetof(%s, %s));' % (s, f, s, c, s, c))
+    for m in macros:
+        v = getattr(_lib, m[len('NKSR_'):])
+        if isinstance(v, tuple):            # a brace initialiser: rows, then every element
+            inner = '[%d]' % len(v[0]) if isinstance(v[0], tuple) else ''
+            lines.append('  { const double a[]%s = %s; const double* p = (const double*)a;' % (inner, m))
+            lines.append('    printf("%s %%zu", sizeof(a) / sizeof(a[0])); for (size_t i = 0; i < sizeof(a) / sizeof(double); ++i) '
+                         'printf(" %%.17g", p[i]); printf("\\n"); }' % m)
+        else:
+            lines.append('  printf("%s %%d %%.17g\\n", (int)std::is_integral<decltype(%s)>::value, (double)(%s));' % (m, m, m))
+    lines += ['  return 0;', '}']
+    (tmp_path / 'probe.cpp').write_text('\n'.join(lines) + '\n')
+    exe = str(tmp_path / 'probe')
+    r = subprocess.run([build.HIPCC, '-x', 'c++', '-std=c++17', '-I', os.path.dirname(build.HEADER), str(tmp_path / 'probe.cpp'), '-o', exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = [l.split() for l in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()]
+    seen = 0
+    for name, key, *vals in out:
+        if name in _lib._STRUCTS:
+            cls = _lib._STRUCTS[name]
+            want = (ctypes.sizeof(cls), 0) if key == '.' else (getattr(cls, key).size, getattr(cls, key).offset)
+            assert (int(vals[0]), int(vals[1])) == want, (name, key, vals, want)
+        else:
+            v = getattr(_lib, name[len('NKSR_'):])
+            if isinstance(v, tuple):
+                assert int(key) == len(v) and [float(x) for x in vals] == _flat(v), (name, vals, v)
+            else:
+                assert bool(int(key)) == isinstance(v, int) and float(vals[0]) == v, (name, key, vals, v)
+        seen += 1
+    assert seen == len(structs) + sum(len(c._fields_) for c in _lib._STRUCTS.values()) + len(macros)
+
+
+def test_header_reader_refuses_what_it_does_not_understand():
+    import pytest
+    from nksr_amd import _cheader
+    for text, quoted in (('int nksr_f(const float* x, long n, void* stream);', 'int nksr_f(const float* x, long n, void* stream)'),
+                         ('typedef struct { int32_t n; int32_t flags : 3; } nksr_x_t;', 'int32_t flags : 3'),
+                         ('int nksr_g(int (*callback)(int), void* stream);', 'int nksr_g(int (*callback)(int), void* stream)'),
+                         ('#define NKSR_N sizeof(int)', '#define NKSR_N sizeof(int)'),
+                         ('typedef struct { float* a[NKSR_UNDEFINED]; } nksr_y_t;', 'float* a[NKSR_UNDEFINED]')):
+        with pytest.raises(_cheader.HeaderError) as e:
+            _cheader.parse(text)
+        assert quoted in str(e.value), str(e.value)
+    ok = _cheader.parse('#define NKSR_K (1ll << 4)\ntypedef struct nksr_s { int32_t a, b[2]; const float* p[NKSR_K]; } nksr_s_t;\n'
+                        'const char* nksr_h(const struct nksr_s* s, size_t* n);')
+    assert ok.consts == {'NKSR_K': 16} and ok.protos == {'nksr_h': ('char*', ['nksr_s_t*', 'size_t*'])}
+    assert ok.structs == {'nksr_s_t': [('a', 'int32_t', None), ('b', 'int32_t', 2), ('p', 'float*', 16)]}
+
+
 def test_product_refuses_cpu_and_never_imports_oracle():
     import sys
     import pytest
