@@ -452,10 +452,6 @@ int nksr_chunk_pair_fill(const nksr_chunk_grid_t* grid, int mode, const float* x
  * gradient when pair_grad / grad_out are given). */
 int nksr_chunk_blend(int64_t n, const int32_t* offsets, const float* pair_w, const float* pair_f, const float* pair_grad,
                      float* f_out, float* grad_out, void* stream);
-/* Halo selection of a batch of chunks, one level (the payload of the rank exchange, SURVEY.md section 8e; chunking.pack_halos):
- * voxel i (keys ascending) belongs to chunk seg = the last of the ascending key ranges klo [nchunk] that starts at or before its key;
- * flag = 1 when its centre (ijk + 0.5) w - shift[seg] lies in one of the chunk's band intervals [tlo, thi] ([nchunk, 3, 2] each, an
- * unused interval = (+inf, -inf)) along some axis. */
 /* Seam candidates of a rank's mesh piece (the merge on rank 0, nksr_amd/dist.py): vertex i lies on the lattice edge (vertex vkey[i],
  * axis[i]); flag = 1 when one of the four lattice cells around that edge belongs to another rank -- owner[chunk of the centre of the
  * cell's base voxel] != rank, base voxel = floor(cell / cells_per_voxel), centre = (base + 0.5) w0, chunk as nksr_chunk_pair_counts. */
@@ -465,6 +461,10 @@ int nksr_edge_seam_flags(const nksr_chunk_grid_t* grid, const int64_t* vkey, con
  * owner[chunk of (x + o)] == rank for an offset o in {-reach, 0, +reach} per split axis (the cells a rank meshes / evaluates). */
 int nksr_points_owner_flags(const nksr_chunk_grid_t* grid, const float* xyz, int64_t n, float reach, const int32_t* owner, int32_t rank,
                             uint8_t* flags_out, void* stream);
+/* Halo selection of a batch of chunks, one level (the payload of the rank exchange, SURVEY.md section 8e; chunking.pack_halos):
+ * voxel i (keys ascending) belongs to chunk seg = the last of the ascending key ranges klo [nchunk] that starts at or before its key;
+ * flag = 1 when its centre (ijk + 0.5) w - shift[seg] lies in one of the chunk's band intervals [tlo, thi] ([nchunk, 3, 2] each, an
+ * unused interval = (+inf, -inf)) along some axis. */
 int nksr_halo_band_flags(const int64_t* keys, const int32_t* ijk, int64_t n, const int64_t* klo, int32_t nchunk, const float* shift,
                          const float* tlo, const float* thi, float w, int32_t* seg_out, int32_t* flags_out, void* stream);
 
@@ -678,6 +678,75 @@ int nksr_mesh_occupancy(const nksr_bvh_t* bvh, const float* query, int64_t nq, c
  * smaller one on a tie; -1 with no faces), point_out [nq, 3]; each optional, not all NULL. */
 int nksr_mesh_closest(const nksr_bvh_t* bvh, const float* query, int64_t nq, const uint32_t* order, float* dist_out, int64_t* face_out,
                       float* point_out, void* stream);
+
+/* ---- mesh topology (nksr_amd/mesh_topology.py: MeshTopology; csrc/meshtopo.hip) ----------------------------
+ * The unique-edge table of a triangle mesh and what follows from it: edge classes, connected components, per-component statistics,
+ * removal of components.  Faces as in the metrics section; here a face with an index outside [0, nv) OR with two equal indices is
+ * INVALID: it has no edges, its component label is -1, it is never kept, and it is counted.  nv < 2^31, nf <= NKSR_TOPO_MAX_FACES
+ * (half-edge ids 3 f + k fit uint32); beyond: NKSR_ERR_ARG.  Every result is an integer (or a min / max), so every array repeats
+ * bit for bit; the one floating-point sum (component areas) goes through nksr_inclusive_sum_by_key_f64.
+ * Build: nksr_topo_halfedge_keys, nksr_sort_pairs_u64_u32 (end_bit = 32 + bit_length(nv); stable, so half-edges of one edge stay in
+ * ascending id order), nksr_topo_run_counts, nksr_exclusive_sum_i64, (read E), nksr_topo_edge_table, nksr_topo_edge_classes. */
+#define NKSR_TOPO_MAX_FACES (1ll << 30)
+#define NKSR_TOPO_BOUNDARY 1        /* edge classes: one incident face                                        */
+#define NKSR_TOPO_INTERIOR 2        /* two, traversing the edge in opposite directions                         */
+#define NKSR_TOPO_MISORIENTED 3     /* two, traversing it in the same direction                                */
+#define NKSR_TOPO_NONMANIFOLD 4     /* more than two                                                           */
+#define NKSR_TOPO_TOTALS 6          /* E, boundary, non-manifold, misoriented edges, invalid faces, referenced vertices */
+/* per face three pairs: key = (min(a, b) << 32) | max(a, b) of half-edge k = (corner k -> corner k + 1), id = 3 f + k; an invalid face
+ * writes the key (nv << 32) | nv, which sorts last.  face_valid_out [nf], vertex_ref_out [nv] (1: named by a valid face; zeroed here). */
+int nksr_topo_halfedge_keys(const void* faces, int faces_int64, int64_t nf, int64_t nv, uint64_t* keys_out, uint32_t* ids_out,
+                            uint8_t* face_valid_out, uint8_t* vertex_ref_out, void* stream);
+/* run heads of the sorted keys: block_counts [nksr_topo_run_blocks(n_half) + 1] = heads per block of sorted positions, then a 0; its
+ * exclusive sum (block_offsets) ends with E */
+int64_t nksr_topo_run_blocks(int64_t n_half);
+int nksr_topo_run_counts(const uint64_t* keys_sorted, int64_t n_half, int64_t nv, int64_t* block_counts, void* stream);
+/* edge e (ascending key): edge_v_out [E, 2] = (min, max); edge_start_out [E + 1] = sorted position of its first half-edge, and at
+ * [E] the number of valid half-edges */
+int nksr_topo_edge_table(const uint64_t* keys_sorted, int64_t n_half, int64_t nv, const int64_t* block_offsets, int64_t n_edges,
+                         int32_t* edge_v_out, uint32_t* edge_start_out, void* stream);
+/* edge_count_out [E] incident valid faces; edge_class_out [E] NKSR_TOPO_*; face_adj_out [nf, 3]: the face across half-edge k, -1 on
+ * a boundary, a non-manifold edge and an invalid face; totals_out [NKSR_TOPO_TOTALS] int64 (integer atomics) */
+int nksr_topo_edge_classes(const void* faces, int faces_int64, int64_t nf, int64_t nv, const uint32_t* ids_sorted, const uint32_t* edge_start,
+                           int64_t n_edges, const uint8_t* vertex_ref, int32_t* edge_count_out, uint8_t* edge_class_out, int32_t* face_adj_out,
+                           int64_t* totals_out, void* stream);
+/* pairs_out [n_half, 2]: (face of sorted half-edge i, face of half-edge i + 1) when both lie on one edge, else (-1, -1): the faces
+ * round an edge -- a non-manifold one too -- in a chain */
+int nksr_topo_face_pairs(const uint64_t* keys_sorted, const uint32_t* ids_sorted, int64_t n_half, int64_t nv, int32_t* pairs_out, void* stream);
+/* Connected components of the graph (nodes [0, n), pairs [n_pairs, 2]; a pair with a negative entry, and a node with valid[i] = 0
+ * (valid may be NULL), take no part).  Union-find: hooks by atomicCAS on parent (the larger root under the smaller), path halving, one
+ * flatten pass; parent[i] = the MINIMUM node index of i's component whatever order the lanes ran in (-1: no part); root_flags_out
+ * [n + 1] = (parent[i] == i), then a 0.  Dense labels: root_rank = nksr_exclusive_sum_i32(root_flags) (its last entry = the number of
+ * components), label_out[i] = root_rank[parent[i]] or -1: ascending label = ascending minimum node index.  n < 2^31. */
+int nksr_uf_components(int32_t* parent, int64_t n, const uint8_t* valid, const int32_t* pairs, int64_t n_pairs, int32_t* root_flags_out,
+                       void* stream);
+int nksr_uf_labels(const int32_t* parent, int64_t n, const int32_t* root_rank, int32_t* label_out, void* stream);
+/* labels of the other kind of node.  from_vertices = 0: vertex_label[v] = the smallest label among the valid faces at v (-1: none);
+ * from_vertices != 0: face_label[f] = vertex_label[first corner of f] (-1 for an invalid face). */
+int nksr_topo_cross_labels(const void* faces, int faces_int64, int64_t nf, int64_t nv, const uint8_t* face_valid, int from_vertices,
+                           int32_t* face_label, int32_t* vertex_label, void* stream);
+/* counts_out [n_comp, 4] int64 (zeroed here): faces, vertices BY THEIR LABEL, edges, boundary edges of every component.  A vertex
+ * where components only touch belongs to each of them: nksr_topo_shared_corners lists the corners whose face is not of the vertex's
+ * label as keys (label << 32) | vertex (keys_out NULL / capacity 0: count only; *count_out = their number, unordered), and
+ * nksr_topo_count_shared adds the distinct keys of the SORTED list to the vertex column. */
+int nksr_topo_component_counts(const int32_t* face_label, int64_t nf, const int32_t* vertex_label, int64_t nv, const uint32_t* ids_sorted,
+                               const uint32_t* edge_start, const uint8_t* edge_class, int64_t n_edges, int64_t n_comp, int64_t* counts_out,
+                               void* stream);
+int nksr_topo_shared_corners(const void* faces, int faces_int64, int64_t nf, int64_t nv, const int32_t* face_label, const int32_t* vertex_label,
+                             uint64_t* keys_out, int64_t capacity, int64_t* count_out, void* stream);
+int nksr_topo_count_shared(const uint64_t* keys_sorted, int64_t m, int64_t n_comp, int64_t* counts, void* stream);
+/* box_out [n_comp, 6] = (min xyz, max xyz) over the corners of every component's faces: order-preserving integer atomics, exact */
+int nksr_topo_component_boxes(const float* v, int64_t nv, const void* faces, int faces_int64, int64_t nf, const int32_t* face_label,
+                              int64_t n_comp, float* box_out, void* stream);
+/* inclusive fp64 sums restarted at every change of the (sorted) key, bitwise reproducible (tmp / tmp_bytes as nksr_exclusive_sum_i32) */
+int nksr_inclusive_sum_by_key_f64(void* tmp, size_t* tmp_bytes, const uint64_t* keys, const double* in, double* out, int64_t n, void* stream);
+/* Compaction by a per-face keep flag.  mark: face_flags_out [nf + 1] = keep && valid (then a 0), vertex_flags_out [nv + 1] = named by
+ * such a face.  After nksr_exclusive_sum_i32 of both: faces_out [kept, 3] (the input's integer type, relative order kept, indices
+ * rewritten), vertex_map_out [nv] int64 = new index or -1. */
+int nksr_topo_compact_mark(const void* faces, int faces_int64, int64_t nf, int64_t nv, const uint8_t* face_keep, int32_t* face_flags_out,
+                           int32_t* vertex_flags_out, void* stream);
+int nksr_topo_compact_faces(const void* faces, int faces_int64, int64_t nf, int64_t nv, const int32_t* face_flags, const int32_t* face_offsets,
+                            const int32_t* vertex_flags, const int32_t* vertex_offsets, void* faces_out, int64_t* vertex_map_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,11 +6,12 @@ use: ``Reconstructor``, ``NKSRNetwork``, ``SparseFeatureH
 ``utils``.  ``import nksr`` resolves to this package through the top-level ``nksr`` shim.
 """
 from . import configs, fields, metrics, svh, utils
+from .mesh_topology import MeshTopology
 from .nn.network import NKSRNetwork
 from .preprocess import get_estimate_normal_preprocess_fn
 from .reconstructor import Reconstructor
 from .svh import SparseFeatureHierarchy
 
-__all__ = ['Reconstructor', 'NKSRNetwork', 'SparseFeatureHierarchy', 'get_estimate_normal_preprocess_fn',
+__all__ = ['Reconstructor', 'NKSRNetwork', 'SparseFeatureHierarchy', 'get_estimate_normal_preprocess_fn', 'MeshTopology',
            'fields', 'svh', 'configs', 'utils', 'metrics']
 __version__ = '0.1.0'

@@ -68,3 +68,15 @@ extern "C" int nksr_inclusive_sum_f64(void* tmp, size_t* tmp_bytes, const double
     NKSR_CHECK_HIP(rocprim::deterministic_inclusive_scan(tmp, *tmp_bytes, in, out, (size_t)n, rocprim::plus<double>(), (hipStream_t)stream));
     return NKSR_OK;
 }
+
+// per-component area sums (mesh topology): the same deterministic look-back, restarted wherever the (sorted) key changes, so a
+// segment's last element holds the sum of that segment alone -- no difference of two long prefix sums
+extern "C" int nksr_inclusive_sum_by_key_f64(void* tmp, size_t* tmp_bytes, const uint64_t* keys, const double* in, double* out, int64_t n,
+                                             void* stream) {
+    if (!tmp_bytes) return nksr_set_error(NKSR_ERR_ARG, "tmp_bytes is NULL");
+    if (n < 0) return nksr_set_error(NKSR_ERR_ARG, "inclusive sum by key: negative size");
+    if (tmp && n > 0 && (!keys || !in || !out)) return nksr_set_error(NKSR_ERR_ARG, "inclusive sum by key: NULL arrays");
+    NKSR_CHECK_HIP(rocprim::deterministic_inclusive_scan_by_key(tmp, *tmp_bytes, keys, in, out, (size_t)n, rocprim::plus<double>(),
+                                                                rocprim::equal_to<uint64_t>(), (hipStream_t)stream));
+    return NKSR_OK;
+}

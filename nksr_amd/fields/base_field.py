@@ -25,6 +25,16 @@ class MeshingResult:
     f: torch.Tensor
     c: Optional[torch.Tensor] = None
 
+    def topology(self):
+        """``MeshTopology`` of this mesh (nksr_amd/mesh_topology.py): edge classes, Euler characteristic, components."""
+        from ..mesh_topology import MeshTopology
+        return MeshTopology(self.v, self.f)
+
+    def remove_small_components(self, min_faces=0, min_area=0.0, min_area_ratio=0.0, keep_largest=None, connectivity='edge'):
+        """A new ``MeshingResult`` without the components below the thresholds (``Components.select``), ``c`` carried through."""
+        v, f, c, _ = self.topology().remove_small_components(min_faces, min_area, min_area_ratio, keep_largest, connectivity, self.c)
+        return MeshingResult(v, f, c)
+
 
 class BaseField:
     def __init__(self, svh):

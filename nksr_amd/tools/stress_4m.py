@@ -29,14 +29,12 @@ def main():
     rowptr, cols, vals, diag = fld.matrix
     res = fld.rhs.double() - solver.spmv(rowptr, cols, vals, fld.alpha).double()
     rel = float(res.norm() / fld.rhs.double().norm())
-    f = mesh.f.long()
+    f = mesh.f
     V = mesh.v.shape[0]
-    e = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
-    key = torch.minimum(e[:, 0], e[:, 1]) * V + torch.maximum(e[:, 0], e[:, 1])
-    _, cnt = torch.unique(key, return_counts=True)
+    topo = mesh.topology()
     print('N=%d M=%d nnz=%d col_format=%d iters=%d rel=%.2e independent residual=%.2e  %.1f ms (%.1f M points/s)  V=%d F=%d open edges=%d non-manifold=%d  peak mem %.1f GB' % (
         n, info['M'], info['nnz'], solver.col_format(cols), info['iters'], info['rel_residual'], rel, dt * 1e3, n / dt / 1e6, V, f.shape[0],
-        int((cnt == 1).sum()), int((cnt > 2).sum()), torch.cuda.max_memory_allocated() / 1e9))
+        topo.boundary_edges, topo.nonmanifold_edges, torch.cuda.max_memory_allocated() / 1e9))
 
 
 if __name__ == '__main__':

@@ -27,16 +27,14 @@ def main():
         dt = time.perf_counter() - t0
         print('rep %d: %.1f ms  %s' % (rep, dt * 1e3, {k: round(v * 1e3, 1) for k, v in rec.timing.items()}), flush=True)
     info = fld.solve_info
-    f = mesh.f.long()
+    f = mesh.f
     V = mesh.v.shape[0]
-    e = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
-    key = torch.minimum(e[:, 0], e[:, 1]) * V + torch.maximum(e[:, 0], e[:, 1])
-    _, cnt = torch.unique(key, return_counts=True)
+    topo = mesh.topology()
     on = fld.evaluate_f(xyz[:: max(1, n // 200_000)].contiguous()).value.abs()
     print('N=%d M=%d stored entries of G,Q=%d iters=%d rel=%.2e alpha finite=%s  %.1f ms (%.1f M points/s)  V=%d F=%d open edges=%d non-manifold=%d  '
           'mean |f| at the input points=%.3e  peak mem %.1f GB' % (
               n, info['M'], fld.stored_entries() or 0, info['iters'], info['rel_residual'], bool(torch.isfinite(fld.alpha).all()), dt * 1e3, n / dt / 1e6,
-              V, f.shape[0], int((cnt == 1).sum()), int((cnt > 2).sum()), float(on.mean()), torch.cuda.max_memory_allocated() / 1e9))
+              V, f.shape[0], topo.boundary_edges, topo.nonmanifold_edges, float(on.mean()), torch.cuda.max_memory_allocated() / 1e9))
 
 
 if __name__ == '__main__':
