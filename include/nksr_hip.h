@@ -526,6 +526,36 @@ int nksr_knn_mean_dist(const float* xyz_sorted, int64_t n, const int32_t* start,
 int nksr_nearest_index(const float* xyz_sorted, const int32_t* start, const int32_t* end, const int64_t* hkeys,
                        const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* query, int64_t nq,
                        int max_ring, int32_t* index_out, void* stream);
+/* The k nearest reference points of arbitrary queries WRITTEN OUT (nksr_amd/cloud.py CloudIndex.knn), 1 <= k <= 32: idx_out [nq, k]
+ * = indices into the sorted cloud, dist2_out [nq, k] = their squared fp32 distances, ascending; valid_out [nq] = 0 where the search
+ * did not reach k points (that row is left untouched: retry on a coarser grid).  query NULL: the queries are the first nq points of
+ * the sorted cloud itself (nq <= n_ref).  exclude_self != 0: ONE reference point is left out of every row -- the one whose sorted
+ * index is self_index[i], or i itself when self_index is NULL; other points at the same position are kept (k + 1 <= n_ref).
+ * _pyramid: every scale in one launch, as nksr_sdf_from_points_pyramid; the plain one: ONE grid, for what the pyramid hands back. */
+int nksr_knn_query_pyramid(const nksr_knn_pyramid_t* pyramid, int64_t n_ref, const float* query, int64_t nq, int k, int exclude_self,
+                           const int32_t* self_index, int max_ring, int32_t* idx_out, float* dist2_out, int32_t* valid_out, void* stream);
+int nksr_knn_query(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                   const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* query, int64_t nq, int k, int exclude_self,
+                   const int32_t* self_index, int max_ring, int32_t* idx_out, float* dist2_out, int32_t* valid_out, void* stream);
+/* count_out [nq] = number of reference points with |x - q|^2 <= radius^2 (fp32, the rounding sequence of the kNN kernels) among the
+ * 27 cells around the query: the grid must have cell >= radius.  cap > 0: the scan of a query stops once its count reaches cap and
+ * min(count, cap) is returned; cap <= 0: no limit.  query / exclude_self / self_index as above.  Integers only, no atomics. */
+int nksr_radius_count(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                      const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* query, int64_t nq, float radius,
+                      int32_t cap, int exclude_self, const int32_t* self_index, int32_t* count_out, void* stream);
+
+/* ---- voxel reduction of a point cloud (csrc/cloud.hip; nksr_amd/cloud.py voxel_downsample) -----------------------------------
+ * order [n] = point indices sorted by voxel key, start / end [n_vox] = the run of every voxel in it (nksr_site_ranges of the sorted
+ * keys).  mean_xyz_out [n_vox, 3] and mean_attr_out [n_vox, C] = the mean of xyz [n, 3] and of attr [n, C] (C = 0: attr and
+ * mean_attr_out NULL; C <= NKSR_VOXEL_REDUCE_MAX_C) over every run, count_out [n_vox] its length.  Sums are fp64 in an order fixed by
+ * (n_vox, start, end, group) alone -- a wavefront owns `group` consecutive voxels and walks their sorted positions 64 at a time, a
+ * segmented tree inside the 64, tile after tile -- divided in fp64 and rounded once to fp32: no atomics, every run repeats bit for
+ * bit.  group: voxels per wavefront, 1 .. 64, 0 = chosen from n_vox.  nearest_out [n_vox] (may be NULL) = the sorted position of the
+ * run's point nearest the (fp64) mean, the lowest position on a tie.  An index of `order` outside [0, n) is left out of sum and count. */
+#define NKSR_VOXEL_REDUCE_MAX_C 16
+int nksr_voxel_reduce(const int32_t* order, int64_t n, const int32_t* start, const int32_t* end, int64_t n_vox, const float* xyz,
+                      const float* attr, int C, int group, float* mean_xyz_out, float* mean_attr_out, int32_t* count_out,
+                      int32_t* nearest_out, void* stream);
 
 /* ---- dual marching cubes (field.extract_dual_mesh, examples/recons_simple.py:27) ------- */
 /* flags[i]=1 where voxel i and its +x,+y,+z,... 7 partners are all active */

@@ -5,8 +5,9 @@ import sys
 
 import nksr_amd
 from nksr_amd import *  # noqa: F401,F403
-from nksr_amd import configs, fields, metrics, svh, utils  # noqa: F401
+from nksr_amd import cloud, configs, fields, metrics, svh, utils  # noqa: F401
 
-for _name in ('configs', 'fields', 'metrics', 'svh', 'utils'):
+for _name in ('cloud', 'configs', 'fields', 'metrics', 'svh', 'utils'):
     sys.modules['nksr.' + _name] = getattr(nksr_amd, _name)
+__all__ = nksr_amd.__all__
 __version__ = nksr_amd.__version__

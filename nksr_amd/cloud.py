@@ -1,0 +1,286 @@
+"""Point-cloud preprocessing on the GPU: k-nearest-neighbour and radius queries, voxel downsampling, outlier masks.
+
+The input side of the tool-chain (``MeshEvaluator`` / ``MeshQuery`` / ``MeshTopology`` are the output side): what a raw lidar or
+photogrammetry scan needs before ``Reconstructor.reconstruct`` -- thinning to a working density and dropping stray returns -- and
+the neighbour search the package already runs for its normals, its SDF ground truth and its metrics, with the indices handed out.
+
+  * ``CloudIndex(xyz)``: the Morton grid and octree of csrc/knn.hip (``normals.PointGrid`` / ``PointPyramid``) built once;
+    ``.knn`` / ``.radius_count`` / ``.mean_knn_distance`` (kernels ``k_knn_query_pyramid``, ``k_knn_query_topk``, ``k_radius_count``).
+  * ``voxel_downsample``: one point per occupied voxel, the mean (or the input point nearest the mean) of every attribute
+    (csrc/cloud.hip ``k_voxel_reduce``: fp64 sums in a fixed order, no atomics, bitwise repeatable).
+  * ``radius_outlier_mask`` / ``statistical_outlier_mask``.
+``nksr_amd.preprocess`` wraps them as ``preprocess_fn`` for ``Reconstructor.reconstruct``.  GPU tensors only.
+"""
+import torch
+
+from . import ops
+from ._lib import call, ptr, require_gpu, stream
+from .ext.sdfgen import _MAX_ROUNDS, _grid_args
+from .normals import PointGrid, PointPyramid, choose_cell_size
+from .svh import inv_w0_f32
+
+MAX_K = 32              # csrc/knn.hip keeps the candidates of a query sorted in registers
+_RINGS = 4              # rings searched per octree level / per grid (ext/sdfgen.py)
+
+
+def _check_points(xyz, cell, what='xyz'):
+    """float32 contiguous [N, 3] on the GPU, finite, |x| / cell below 2^20 -- the checks of ``svh._check_xyz`` (one readback)."""
+    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
+        raise RuntimeError('%s must be a floating-point [N,3] tensor' % what)
+    require_gpu(xyz.device)
+    xyz = xyz.to(torch.float32).contiguous()
+    if xyz.shape[0]:
+        amax = float(xyz.abs().max())
+        if not (amax * inv_w0_f32(cell) < (1 << 20) - 8):            # also catches NaN / inf
+            raise RuntimeError('%s: coordinates non-finite or out of range: |x| / cell must stay below 2^20 (got %g); recentre the '
+                               'cloud or use a larger cell' % (what, amax * inv_w0_f32(cell)))
+    return xyz
+
+
+def _amax(xyz):
+    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
+        raise RuntimeError('xyz must be a floating-point [N,3] tensor')
+    require_gpu(xyz.device)
+    amax = float(xyz.abs().max()) if xyz.shape[0] else 0.0
+    if not amax < float('inf'):
+        raise RuntimeError('non-finite coordinates in the input')
+    return amax
+
+
+class CloudIndex:
+    """Neighbour queries on one cloud.  ``xyz``: [N, 3] GPU tensor, N >= 1.  Indices that come back refer to the caller's order."""
+
+    def __init__(self, xyz):
+        amax = _amax(xyz)
+        if xyz.shape[0] < 1:
+            raise ValueError('CloudIndex: empty cloud')
+        x32 = xyz.to(torch.float32).contiguous()
+        # the cell of the normals / sdfgen searches (a few times 8 points per 3^3 block), kept wide enough for the cloud's coordinates
+        # to stay inside the key range whatever its density (a single point, a thousand duplicates)
+        cell = max(choose_cell_size(x32, 8), amax * 2.0 ** -15, 1e-9)
+        self.xyz = _check_points(x32, cell)
+        self.n = self.xyz.shape[0]
+        self.device = self.xyz.device
+        self.amax = amax
+        self.pyramid = PointPyramid(PointGrid(self.xyz, cell))
+        self.pg = self.pyramid.pg
+        self._radius_grids = {}
+
+    # ---- helpers -------------------------------------------------------------------------------------------------------------
+    def _queries(self, query, cell):
+        q = _check_points(query, cell, 'query')
+        if q.device != self.device:
+            raise RuntimeError('query is on %s, the cloud on %s' % (q.device, self.device))
+        return q
+
+    def _ranks(self, pg):
+        """sorted position of every (caller-order) point in grid ``pg``"""
+        rank = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        rank[pg.perm] = torch.arange(self.n, dtype=torch.int32, device=self.device)
+        return rank
+
+    # ---- k nearest neighbours ------------------------------------------------------------------------------------------------
+    def knn(self, k, query=None, exclude_self=False):
+        """-> (idx int64 [Q, k], dist float32 [Q, k] ascending).  ``query=None``: the cloud itself, row i = point i.  ``exclude_self``
+        (self-queries only): point i is left out of its own row; other points at the same position are not."""
+        k = int(k)
+        ex = bool(exclude_self)
+        if k < 1 or k > MAX_K:
+            raise ValueError('knn: 1 <= k <= %d (got %d)' % (MAX_K, k))
+        if k + ex > self.n:
+            raise ValueError('knn: k = %d%s of a cloud of %d points' % (k, ' other points' if ex else '', self.n))
+        if ex and query is not None:
+            raise ValueError('knn: exclude_self needs query=None (the cloud itself)')
+        dev, pg = self.device, self.pg
+        if query is None:
+            q, nq = None, self.n
+        else:
+            q = self._queries(query, pg.cell)
+            nq = q.shape[0]
+        idx = torch.zeros((nq, k), dtype=torch.int32, device=dev)        # (zeroed: a row the search hands back is not written)
+        d2 = torch.zeros((nq, k), dtype=torch.float32, device=dev)
+        valid = torch.empty(nq, dtype=torch.int32, device=dev)
+        call('nksr_knn_query_pyramid', self.pyramid.struct, self.n, ptr(q), nq, k, int(ex), None, _RINGS, ptr(idx), ptr(d2), ptr(valid),
+             stream())
+        ok = valid > 0
+        out_idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        if query is None:               # rows are in sorted order: back to the caller's
+            out_idx[pg.perm] = pg.perm[idx.long()]
+            out_d2 = torch.empty_like(d2)
+            out_d2[pg.perm] = d2
+            okc = torch.empty_like(ok)
+            okc[pg.perm] = ok
+            ok = okc
+        else:
+            out_idx[:] = pg.perm[idx.long()]
+            out_d2 = d2
+        todo = torch.nonzero(~ok).flatten()
+        # what the octree hands back (farther from the cloud than its top level reaches): single grids, 4x coarser per round
+        cell = self.pyramid.top_cell * 2.0
+        for _ in range(_MAX_ROUNDS):
+            if not todo.numel():
+                break
+            g = PointGrid(self.xyz, cell)
+            m = todo.numel()
+            qs = (self.xyz[todo] if query is None else q[todo]).contiguous()
+            me = self._ranks(g)[todo].contiguous() if ex else None
+            i2 = torch.empty((m, k), dtype=torch.int32, device=dev)
+            s2 = torch.empty((m, k), dtype=torch.float32, device=dev)
+            v2 = torch.empty(m, dtype=torch.int32, device=dev)
+            call('nksr_knn_query', ptr(g.xyz), self.n, *_grid_args(g), ptr(qs), m, k, int(ex), ptr(me), _RINGS, ptr(i2), ptr(s2), ptr(v2),
+                 stream())
+            good = v2 > 0
+            rows = todo[good]
+            out_idx[rows] = g.perm[i2[good].long()]
+            out_d2[rows] = s2[good]
+            todo = todo[~good]
+            cell *= 4.0
+        if todo.numel():
+            raise RuntimeError('knn: %d queries found no %d neighbours' % (todo.numel(), k))
+        return out_idx, torch.sqrt(out_d2)
+
+    def mean_knn_distance(self, k):
+        """float32 [N]: mean distance of every point to its k nearest OTHER points (the mean is taken in fp64 and rounded once)."""
+        _, dist = self.knn(k, exclude_self=True)
+        return dist.double().mean(dim=1).float()
+
+    # ---- fixed-radius neighbour count ----------------------------------------------------------------------------------------
+    def _radius_grid(self, radius):
+        """A grid whose cell is >= radius: 2 % above it -- the fp32 product that bins a point is off by at most 2^-24 |x| / cell cells,
+        < 2^-9 with the floor below -- and never so fine that the cloud's coordinates leave the key range."""
+        if radius not in self._radius_grids:
+            self._radius_grids.clear()                  # (one at a time: a grid is as large as the cloud)
+            self._radius_grids[radius] = PointGrid(self.xyz, max(radius * 1.02, self.amax * 2.0 ** -15))
+        return self._radius_grids[radius]
+
+    def radius_count(self, radius, query=None, cap=None, exclude_self=False):
+        """-> int32 [Q]: the number of cloud points within ``radius`` of every query (``query=None``: of every point of the cloud,
+        itself counted unless ``exclude_self``).  ``cap``: counting stops there, the result is min(count, cap)."""
+        radius = float(radius)
+        if not (0.0 < radius < float('inf')):
+            raise ValueError('radius_count: radius must be positive and finite (got %r)' % radius)
+        ex = bool(exclude_self)
+        if ex and query is not None:
+            raise ValueError('radius_count: exclude_self needs query=None (the cloud itself)')
+        if cap is not None and int(cap) < 1:
+            raise ValueError('radius_count: cap must be >= 1 (got %r)' % cap)
+        g = self._radius_grid(radius)
+        dev = self.device
+        if query is None:
+            q, nq = None, self.n
+        else:
+            q = self._queries(query, g.cell)
+            nq = q.shape[0]
+        cnt = torch.empty(nq, dtype=torch.int32, device=dev)
+        call('nksr_radius_count', ptr(g.xyz), self.n, *_grid_args(g), ptr(q), nq, radius, int(cap) if cap is not None else 0, int(ex), None,
+             ptr(cnt), stream())
+        if query is not None:
+            return cnt
+        out = torch.empty_like(cnt)
+        out[g.perm] = cnt
+        return out
+
+
+# ---- voxel downsampling ------------------------------------------------------------------------------------------------------------
+class VoxelDownsample:
+    """Result of ``voxel_downsample``: ``xyz`` [V, 3], ``normal`` / ``sensor`` / ``color`` ([V, C] or None), ``count`` int32 [V] points
+    per voxel, ``inverse`` int64 [N] = the output row of every input point, ``index`` int64 [V] = the representative input point
+    (``reduce='nearest'`` only, else None).  Rows are in ascending voxel-key order."""
+
+    def __init__(self, xyz, normal, sensor, color, count, inverse, index):
+        self.xyz, self.normal, self.sensor, self.color, self.count, self.inverse, self.index = xyz, normal, sensor, color, count, inverse, index
+
+    def __len__(self):
+        return int(self.xyz.shape[0])
+
+
+def voxel_runs(xyz, voxel_size):
+    """The cloud grouped by voxel: (order int32 [N] = point indices sorted by voxel key -- stable, so ascending inside a voxel --,
+    keys int64 [V] ascending, start / end int32 [V] = every voxel's run in ``order``).  Voxel of a point:
+    floor(fl32(x) * inv_w0_f32(voxel_size)) per axis, the hierarchy's definition (nksr_point_keys)."""
+    n, dev = xyz.shape[0], xyz.device
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    call('nksr_point_keys', ptr(xyz), n, inv_w0_f32(voxel_size), ptr(keys), stream())
+    ks, order = ops.sort_pairs(keys, torch.arange(n, dtype=torch.int32, device=dev))
+    ukeys = ops.unique_sorted(ks)
+    nv = ukeys.numel()
+    start = torch.empty(nv, dtype=torch.int32, device=dev)
+    end = torch.empty(nv, dtype=torch.int32, device=dev)
+    call('nksr_site_ranges', ptr(ks), n, ptr(ukeys), nv, 0, ptr(start), ptr(end), stream())
+    return order, ukeys, start, end
+
+
+def voxel_reduce(order, start, end, xyz, attr=None, nearest=False, group=0):
+    """csrc/cloud.hip: -> (mean xyz [V, 3], mean attr [V, C] or None, count int32 [V], nearest int32 [V] or None = the position in
+    ``order`` of every run's point nearest its mean).  ``group``: voxels per wavefront, 0 = chosen from V."""
+    n, nv, dev = xyz.shape[0], start.numel(), xyz.device
+    c = 0 if attr is None else int(attr.shape[1])
+    mean = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    amean = torch.empty((nv, c), dtype=torch.float32, device=dev) if c else None
+    count = torch.empty(nv, dtype=torch.int32, device=dev)
+    near = torch.empty(nv, dtype=torch.int32, device=dev) if nearest else None
+    call('nksr_voxel_reduce', ptr(order), n, ptr(start), ptr(end), nv, ptr(xyz), ptr(attr) if c else None, c, int(group), ptr(mean),
+         ptr(amean), ptr(count), ptr(near), stream())
+    return mean, amean, count, near
+
+
+def voxel_downsample(xyz, voxel_size, normal=None, sensor=None, color=None, reduce='mean'):
+    """One point per occupied voxel of size ``voxel_size``.  ``reduce='mean'``: position and every attribute are the mean over the
+    voxel's points; a mean normal is scaled back to unit length (one shorter than 1e-12 -- opposing normals -- is replaced by the normal
+    of the voxel's lowest-index point).  ``reduce='nearest'``: the input point nearest the mean (the lowest index on a tie) stands for
+    the voxel, with its own attributes.  -> ``VoxelDownsample``."""
+    if reduce not in ('mean', 'nearest'):
+        raise ValueError("voxel_downsample: reduce must be 'mean' or 'nearest' (got %r)" % (reduce,))
+    voxel_size = float(voxel_size)
+    if not (0.0 < voxel_size < float('inf')):
+        raise ValueError('voxel_downsample: voxel_size must be positive and finite (got %r)' % voxel_size)
+    xyz = _check_points(xyz, voxel_size)
+    n, dev = xyz.shape[0], xyz.device
+    given = [(name, a) for name, a in (('normal', normal), ('sensor', sensor), ('color', color)) if a is not None]
+    for name, a in given:
+        if a.dim() != 2 or a.shape[0] != n or a.device != dev:
+            raise RuntimeError('voxel_downsample: %s must be a [N, C] tensor on the device of xyz' % name)
+    if n == 0:
+        empty = {name: a.to(torch.float32).reshape(0, a.shape[1]) for name, a in given}
+        return VoxelDownsample(xyz, empty.get('normal'), empty.get('sensor'), empty.get('color'), torch.empty(0, dtype=torch.int32, device=dev),
+                               torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev) if reduce == 'nearest' else None)
+    attr = torch.cat([a.to(torch.float32) for _, a in given], dim=1).contiguous() if given else None
+    order, ukeys, start, end = voxel_runs(xyz, voxel_size)
+    nearest = reduce == 'nearest'
+    mean, amean, count, near = voxel_reduce(order, start, end, xyz, attr, nearest=nearest)
+    nv = ukeys.numel()
+    inverse = torch.empty(n, dtype=torch.int64, device=dev)
+    inverse[order.long()] = torch.repeat_interleave(torch.arange(nv, device=dev), (end - start).long(), output_size=n)
+    index = None
+    if nearest:
+        index = order.long()[near.long()]
+        mean = xyz[index]
+        amean = attr[index] if attr is not None else None
+    out, col = {'normal': None, 'sensor': None, 'color': None}, 0
+    for name, a in given:
+        out[name] = amean[:, col:col + a.shape[1]].contiguous()
+        col += a.shape[1]
+    if out['normal'] is not None and not nearest:
+        m = out['normal'].double()
+        length = m.norm(dim=1, keepdim=True)
+        first = normal.to(torch.float32)[order.long()[start.long()]]
+        out['normal'] = torch.where(length < 1e-12, first, (m / length.clamp_min(1e-300)).float())
+    return VoxelDownsample(mean, out['normal'], out['sensor'], out['color'], count, inverse, index)
+
+
+# ---- outlier masks -----------------------------------------------------------------------------------------------------------------
+def radius_outlier_mask(xyz, radius, min_neighbors):
+    """bool [N]: True where a point has at least ``min_neighbors`` OTHER points within ``radius``."""
+    m = int(min_neighbors)
+    if xyz.shape[0] == 0 or m <= 0:
+        require_gpu(xyz.device)
+        return torch.ones(xyz.shape[0], dtype=torch.bool, device=xyz.device)
+    return CloudIndex(xyz).radius_count(radius, cap=m, exclude_self=True) >= m
+
+
+def statistical_outlier_mask(xyz, k=16, std_ratio=2.0):
+    """bool [N]: True where m_i <= mu + std_ratio * sigma, m_i = the mean distance of point i to its k nearest other points, mu / sigma =
+    mean and sample standard deviation (N - 1) of m, reduced in fp64 on the device."""
+    m = CloudIndex(xyz).mean_knn_distance(k).double()
+    sigma = m.std(unbiased=True) if m.numel() > 1 else m.new_zeros(())
+    return m <= m.mean() + float(std_ratio) * sigma

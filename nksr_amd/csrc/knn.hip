@@ -1180,3 +1180,159 @@ extern "C" int nksr_nn_metrics(const nksr_knn_pyramid_t* pyramid, const int64_t*
     NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
+
+// ---- the k nearest WRITTEN OUT, and the points within a radius counted (nksr_amd/cloud.py) ---------------------------------------------
+// The searches are the ones above (knn_topk_pyramid / knn_topk, one thread per query, the block shape and LDS stacks of k_sdf_pyramid);
+// the new work is the stores.  exclude_self: the list is searched with one slot more (kk = k + 1) and the query's own point dropped
+// from it on the way out -- it is the nearest candidate or tied with it at distance 0, so it is in the list unless kk OTHER points
+// lie at distance 0 too, and then the first k of the list are k nearest others all the same.  Points that merely share the
+// position stay.  (kk = 33 takes a list of its own size: TopK<33>.)
+template <int KMAX>
+__device__ __forceinline__ void knn_write(const TopK<KMAX>& top, int kk, int k, int self, int64_t i, int32_t* __restrict__ idx_out,
+                                          float* __restrict__ d2_out) {
+    int w = 0;
+    bool skip = self >= 0;
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) {
+        if (j < KMAX - kk) continue;
+        if (skip && top.idx[j] == self) { skip = false; continue; }
+        if (w < k) {
+            idx_out[i * k + w] = top.idx[j];
+            d2_out[i * k + w] = top.d2[j];
+            ++w;
+        }
+    }
+}
+template <int KMAX>
+__global__ void __launch_bounds__(KNN_PYR_BLOCK) k_knn_query_pyramid(KnnPyramid Parg, const float* __restrict__ query, int64_t nq, int k, int exclude_self,
+                                                                     const int32_t* __restrict__ self_index, int max_ring,
+                                                                     int32_t* __restrict__ idx_out, float* __restrict__ d2_out,
+                                                                     int32_t* __restrict__ valid) {
+    __shared__ int s_node[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
+    __shared__ unsigned char s_cursor[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
+    __shared__ KnnPyramid P;
+    if (threadIdx.x == 0) P = Parg;
+    __syncthreads();
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const float* qp = query ? query + i * 3 : P.xyz + i * 3;
+    const float q[3] = {qp[0], qp[1], qp[2]};
+    const int kk = k + (exclude_self ? 1 : 0);
+    TopK<KMAX> top;
+    if (!knn_topk_pyramid<KMAX>(P, q, kk, max_ring, top, &s_node[0][threadIdx.x], &s_cursor[0][threadIdx.x])) { valid[i] = 0; return; }
+    valid[i] = 1;
+    knn_write<KMAX>(top, kk, k, exclude_self ? (self_index ? self_index[i] : (int)i) : -1, i, idx_out, d2_out);
+}
+template <int KMAX>
+__global__ void __launch_bounds__(128) k_knn_query_topk(KnnGrid g, const float* __restrict__ query, int64_t nq, int k, int exclude_self,
+                                                        const int32_t* __restrict__ self_index, int max_ring, int32_t* __restrict__ idx_out,
+                                                        float* __restrict__ d2_out, int32_t* __restrict__ valid) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const float* qp = query ? query + i * 3 : g.xyz + i * 3;
+    const float q[3] = {qp[0], qp[1], qp[2]};
+    const int kk = k + (exclude_self ? 1 : 0);
+    TopK<KMAX> top;
+    if (!knn_topk<KMAX>(g, q, kk, max_ring, top)) { valid[i] = 0; return; }
+    valid[i] = 1;
+    knn_write<KMAX>(top, kk, k, exclude_self ? (self_index ? self_index[i] : (int)i) : -1, i, idx_out, d2_out);
+}
+// One thread per query, the 27 cells around it (cell >= radius: nothing within the radius lies outside them), candidates four at a time
+// like knn_scan.  The count may pass `cap` by the rest of a group of four before the scan stops: clamped at the end.
+__global__ void __launch_bounds__(128) k_radius_count(KnnGrid g, const float* __restrict__ query, int64_t nq, float r2, int cap, int exclude_self,
+                                                      const int32_t* __restrict__ self_index, int32_t* __restrict__ count) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const float* qp = query ? query + i * 3 : g.xyz + i * 3;
+    const float q[3] = {qp[0], qp[1], qp[2]};
+    const int self = exclude_self ? (self_index ? self_index[i] : (int)i) : -1;
+    int c[3];
+    cell_of(g, q, c);
+    int n = 0;
+    for (int j = 0; j < 27 && n < cap; ++j) {
+        const int ci = hash_find(g.hkeys, g.hvals, g.hcap, morton_biased(c[0] + j / 9 - 1, c[1] + (j / 3) % 3 - 1, c[2] + j % 3 - 1, NKSR_BIAS0));
+        if (ci < 0) continue;
+        const int e = g.end[ci];
+        int kk = g.start[ci];
+        for (; kk + 4 <= e && n < cap; kk += 4) {
+            float p[12];
+#pragma unroll
+            for (int t = 0; t < 12; ++t) p[t] = g.xyz[kk * 3 + t];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) n += (kk + t != self) && knn_d2(p[3 * t] - q[0], p[3 * t + 1] - q[1], p[3 * t + 2] - q[2]) <= r2;
+        }
+        if (n >= cap) break;
+        for (; kk < e; ++kk) n += (kk != self) && knn_d2(g.xyz[kk * 3] - q[0], g.xyz[kk * 3 + 1] - q[1], g.xyz[kk * 3 + 2] - q[2]) <= r2;
+    }
+    count[i] = n < cap ? n : cap;
+}
+
+static int knn_query_args(const char* who, int64_t n_ref, const float* query, int64_t nq, int k, int exclude_self, int max_ring,
+                          const void* idx_out, const void* d2_out, const void* valid_out) {
+    if (nq < 0 || n_ref < 0) return nksr_set_error(NKSR_ERR_ARG, "%s: negative size (nq=%lld, n_ref=%lld)", who, (long long)nq, (long long)n_ref);
+    if (k < 1 || k > 32) return nksr_set_error(NKSR_ERR_ARG, "%s: 1 <= k <= 32 (got %d)", who, k);
+    if (k + (exclude_self ? 1 : 0) > n_ref)
+        return nksr_set_error(NKSR_ERR_ARG, "%s: k = %d%s of %lld reference points", who, k, exclude_self ? " others" : "", (long long)n_ref);
+    if (!query && nq > n_ref) return nksr_set_error(NKSR_ERR_ARG, "%s: query NULL (the cloud itself) with nq = %lld > n_ref = %lld", who, (long long)nq, (long long)n_ref);
+    if (max_ring < 1) return nksr_set_error(NKSR_ERR_ARG, "%s: max_ring must be >= 1 (got %d)", who, max_ring);
+    if (nq > 0 && (!idx_out || !d2_out || !valid_out)) return nksr_set_error(NKSR_ERR_ARG, "%s: NULL output arrays", who);
+    return NKSR_OK;
+}
+extern "C" int nksr_knn_query_pyramid(const nksr_knn_pyramid_t* pyramid, int64_t n_ref, const float* query, int64_t nq, int k, int exclude_self,
+                                      const int32_t* self_index, int max_ring, int32_t* idx_out, float* dist2_out, int32_t* valid_out, void* stream) {
+    if (int rc = knn_query_args("knn query (pyramid)", n_ref, query, nq, k, exclude_self, max_ring, idx_out, dist2_out, valid_out)) return rc;
+    KnnPyramid P;
+    if (int rc = make_pyramid(P, pyramid)) return rc;
+    if (nq == 0) return NKSR_OK;
+    const dim3 gr(nksr_blocks(nq, KNN_PYR_BLOCK)), bl(KNN_PYR_BLOCK);
+    const int kk = k + (exclude_self ? 1 : 0);
+#define KNN_Q(KM) hipLaunchKernelGGL((k_knn_query_pyramid<KM>), gr, bl, 0, (hipStream_t)stream, P, query, nq, k, exclude_self, self_index, max_ring, idx_out, dist2_out, valid_out)
+    if (kk <= 8) KNN_Q(8);
+    else if (kk <= 16) KNN_Q(16);
+    else if (kk <= 32) KNN_Q(32);
+    else KNN_Q(33);
+#undef KNN_Q
+    NKSR_CHECK_LAUNCH();
+    return NKSR_OK;
+}
+static int knn_grid_args(const char* who, const float* xyz_sorted, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                         const int32_t* hvals, int32_t hcap, float cell, float inv_cell) {
+    if (!xyz_sorted || !start || !end || !hkeys || !hvals) return nksr_set_error(NKSR_ERR_ARG, "%s: NULL grid arrays", who);
+    if (hcap < 8 || (hcap & (hcap - 1))) return nksr_set_error(NKSR_ERR_ARG, "%s: hcap must be a power of two >= 8 (got %d)", who, hcap);
+    if (!(cell > 0.f) || !(inv_cell > 0.f)) return nksr_set_error(NKSR_ERR_ARG, "%s: cell and inv_cell must be > 0", who);
+    return NKSR_OK;
+}
+extern "C" int nksr_knn_query(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                              const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* query, int64_t nq, int k, int exclude_self,
+                              const int32_t* self_index, int max_ring, int32_t* idx_out, float* dist2_out, int32_t* valid_out, void* stream) {
+    if (int rc = knn_query_args("knn query", n_ref, query, nq, k, exclude_self, max_ring, idx_out, dist2_out, valid_out)) return rc;
+    if (int rc = knn_grid_args("knn query", xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell)) return rc;
+    if (nq == 0) return NKSR_OK;
+    KnnGrid g = make_grid(xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell);
+    const dim3 gr(nksr_blocks(nq, 128)), bl(128);
+    const int kk = k + (exclude_self ? 1 : 0);
+#define KNN_Q(KM) hipLaunchKernelGGL((k_knn_query_topk<KM>), gr, bl, 0, (hipStream_t)stream, g, query, nq, k, exclude_self, self_index, max_ring, idx_out, dist2_out, valid_out)
+    if (kk <= 8) KNN_Q(8);
+    else if (kk <= 16) KNN_Q(16);
+    else if (kk <= 32) KNN_Q(32);
+    else KNN_Q(33);
+#undef KNN_Q
+    NKSR_CHECK_LAUNCH();
+    return NKSR_OK;
+}
+extern "C" int nksr_radius_count(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                                 const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* query, int64_t nq, float radius,
+                                 int32_t cap, int exclude_self, const int32_t* self_index, int32_t* count_out, void* stream) {
+    if (nq < 0 || n_ref < 0) return nksr_set_error(NKSR_ERR_ARG, "radius count: negative size (nq=%lld, n_ref=%lld)", (long long)nq, (long long)n_ref);
+    if (!(radius > 0.f) || !(radius < 3.4e38f)) return nksr_set_error(NKSR_ERR_ARG, "radius count: radius must be positive and finite");
+    if (int rc = knn_grid_args("radius count", xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell)) return rc;
+    if (!(cell >= radius)) return nksr_set_error(NKSR_ERR_ARG, "radius count: the grid's cell (%g) must be >= radius (%g)", (double)cell, (double)radius);
+    if (!query && nq > n_ref) return nksr_set_error(NKSR_ERR_ARG, "radius count: query NULL (the cloud itself) with nq = %lld > n_ref = %lld", (long long)nq, (long long)n_ref);
+    if (nq > 0 && !count_out) return nksr_set_error(NKSR_ERR_ARG, "radius count: NULL output array");
+    if (nq == 0) return NKSR_OK;
+    KnnGrid g = make_grid(xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell);
+    hipLaunchKernelGGL(k_radius_count, dim3(nksr_blocks(nq, 128)), dim3(128), 0, (hipStream_t)stream, g, query, nq, radius * radius,
+                       cap > 0 ? (int)cap : 0x7fffffff, exclude_self, self_index, count_out);
+    NKSR_CHECK_LAUNCH();
+    return NKSR_OK;
+}

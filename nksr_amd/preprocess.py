@@ -1,11 +1,56 @@
-"""``nksr.get_estimate_normal_preprocess_fn(knn, deg)`` (reference call sites
+"""``preprocess_fn`` makers for ``Reconstructor.reconstruct(..., preprocess_fn=...)``: every one returns a function
+``(xyz, normal, sensor) -> (xyz', normal', sensor')`` (``None`` passes through as ``None``).
+
+``nksr.get_estimate_normal_preprocess_fn(knn, deg)`` (reference call sites
 examples/recons_waymo.py:36, gis_app.py:41; CPU recipe examples/recons_waymo_cpu.py:21-41):
 kNN-PCA normals, flipped towards the sensor, grazing (> deg) points dropped.
-SURVEY.md section 8(f)-1 ranks this "next"; the HIP implementation lands after the hot path."""
+
+The cleaning steps in front of it (nksr_amd/cloud.py): voxel downsampling and the two outlier filters, chained with
+``compose_preprocess_fns``.  The filters keep the input order of the points they keep; the downsampler returns its voxels in
+ascending key order."""
 
 
 def get_estimate_normal_preprocess_fn(knn=64, deg=85.0):
     def fn(xyz, normal, sensor):
         from .normals import estimate_normals_knn
         return estimate_normals_knn(xyz, normal, sensor, int(knn), float(deg))
+    return fn
+
+
+def get_voxel_downsample_preprocess_fn(voxel_size, reduce='mean'):
+    """One point per voxel of size ``voxel_size`` (``cloud.voxel_downsample``; colours do not fit the three slots: call it directly)."""
+    def fn(xyz, normal, sensor):
+        from .cloud import voxel_downsample
+        r = voxel_downsample(xyz, voxel_size, normal=normal, sensor=sensor, reduce=reduce)
+        return r.xyz, r.normal, r.sensor
+    return fn
+
+
+def _select(mask, xyz, normal, sensor):
+    return xyz[mask], normal[mask] if normal is not None else None, sensor[mask] if sensor is not None else None
+
+
+def get_radius_outlier_preprocess_fn(radius, min_neighbors):
+    """Keeps the points with at least ``min_neighbors`` other points within ``radius`` (``cloud.radius_outlier_mask``)."""
+    def fn(xyz, normal, sensor):
+        from .cloud import radius_outlier_mask
+        return _select(radius_outlier_mask(xyz, radius, min_neighbors), xyz, normal, sensor)
+    return fn
+
+
+def get_statistical_outlier_preprocess_fn(k=16, std_ratio=2.0):
+    """Keeps the points whose mean distance to their k nearest neighbours is at most mean + std_ratio * std over the cloud
+    (``cloud.statistical_outlier_mask``)."""
+    def fn(xyz, normal, sensor):
+        from .cloud import statistical_outlier_mask
+        return _select(statistical_outlier_mask(xyz, k, std_ratio), xyz, normal, sensor)
+    return fn
+
+
+def compose_preprocess_fns(*fns):
+    """The given functions applied one after the other, e.g. outlier filter -> downsample -> get_estimate_normal_preprocess_fn."""
+    def fn(xyz, normal, sensor):
+        for f in fns:
+            xyz, normal, sensor = f(xyz, normal, sensor)
+        return xyz, normal, sensor
     return fn
