@@ -483,10 +483,11 @@ int nksr_knn_pca_normals(const float* xyz_sorted, int64_t n, const int32_t* star
  * of size cell * 2^l, its cell keys are the level-0 keys >> 3 l (sorted unique); start / end = the point range of every cell, hkeys /
  * hvals / hcap the key -> cell hash of the level, and for l > 0 child [n_l + 1] / cmask [n_l] = the range of a cell's children on level
  * l - 1 and their occupied octants (nksr_knn_pyramid_level builds start / end / child / cmask of a level from the level below).
- * nksr_sdf_from_points_pyramid / nksr_knn_mean_dist_pyramid = nksr_sdf_from_points / nksr_knn_mean_dist for nb_points <= 32 over
- * EVERY scale in one launch: a query climbs to the first level with a point within one cell of it and takes its k nearest there
- * (kept sorted in registers; cells nearest first, descended with box pruning down to cells of <= leaf points), climbing on only when
- * fewer than k lie within max_ring rings; valid = 0: not even the coarsest level holds k points in reach. */
+ * nksr_sdf_from_points_pyramid / nksr_knn_mean_dist_pyramid = the nb_points <= 32 path of nksr_sdf_from_points / nksr_knn_mean_dist
+ * at every scale, EVERY level in one launch: a query climbs to the first level with a point within one cell of it and takes its k
+ * nearest there (kept sorted in registers; cells nearest first, descended with box pruning down to cells of <= leaf points), climbing on
+ * only when fewer than k lie within max_ring rings; valid = 0: not even the coarsest level holds k points in reach.  levels = 1 (no
+ * child / cmask) is a single grid: what the host retries such rows on, with a coarser cell. */
 #define NKSR_KNN_LEVELS 12
 typedef struct {
     const float* xyz_sorted;
@@ -513,7 +514,8 @@ int nksr_knn_mean_dist_pyramid(const nksr_knn_pyramid_t* pyramid, int64_t n, int
  * (|n.(x-p)| inside stdv * ref_std[p], |x-p| outside) with the sign voted by the k neighbours; imls != 0: IMLS weights
  * exp(-|x-p_k|^2 / stdv^2).  ref_std_sorted may be NULL (= 1); grad_out may be NULL.  valid_out[i] = 0: fewer than k points within
  * max_ring cells (retry on a coarser grid).  nksr_knn_mean_dist: mean distance of every reference point to its k nearest
- * (itself included) = ref_std for adaptive_knn = k. */
+ * (itself included) = ref_std for adaptive_knn = k.  These two are the ANY-k path: one grid, the k-th distance found by bisection
+ * (~35 scans of the candidate block per query); the host sends them nb_points > 32 only. */
 int nksr_sdf_from_points(const float* xyz_sorted, const float* normal_sorted, const float* ref_std_sorted, const int32_t* start,
                          const int32_t* end, const int64_t* hkeys, const int32_t* hvals, int32_t hcap, float cell, float inv_cell,
                          const float* query, int64_t nq, int k, int max_ring, float stdv, int imls, float* sdf_out, float* grad_out,
@@ -531,12 +533,9 @@ int nksr_nearest_index(const float* xyz_sorted, const int32_t* start, const int3
  * did not reach k points (that row is left untouched: retry on a coarser grid).  query NULL: the queries are the first nq points of
  * the sorted cloud itself (nq <= n_ref).  exclude_self != 0: ONE reference point is left out of every row -- the one whose sorted
  * index is self_index[i], or i itself when self_index is NULL; other points at the same position are kept (k + 1 <= n_ref).
- * _pyramid: every scale in one launch, as nksr_sdf_from_points_pyramid; the plain one: ONE grid, for what the pyramid hands back. */
+ * The search is that of nksr_sdf_from_points_pyramid. */
 int nksr_knn_query_pyramid(const nksr_knn_pyramid_t* pyramid, int64_t n_ref, const float* query, int64_t nq, int k, int exclude_self,
                            const int32_t* self_index, int max_ring, int32_t* idx_out, float* dist2_out, int32_t* valid_out, void* stream);
-int nksr_knn_query(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,
-                   const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* query, int64_t nq, int k, int exclude_self,
-                   const int32_t* self_index, int max_ring, int32_t* idx_out, float* dist2_out, int32_t* valid_out, void* stream);
 /* count_out [nq] = number of reference points with |x - q|^2 <= radius^2 (fp32, the rounding sequence of the kNN kernels) among the
  * 27 cells around the query: the grid must have cell >= radius.  cap > 0: the scan of a query stops once its count reaches cap and
  * min(count, cap) is returned; cap <= 0: no limit.  query / exclude_self / self_index as above.  Integers only, no atomics. */

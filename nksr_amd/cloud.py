@@ -4,8 +4,8 @@ The input side of the tool-chain (``MeshEvaluator`` / ``MeshQuery`` / ``MeshTopo
 photogrammetry scan needs before ``Reconstructor.reconstruct`` -- thinning to a working density and dropping stray returns -- and
 the neighbour search the package already runs for its normals, its SDF ground truth and its metrics, with the indices handed out.
 
-  * ``CloudIndex(xyz)``: the Morton grid and octree of csrc/knn.hip (``normals.PointGrid`` / ``PointPyramid``) built once;
-    ``.knn`` / ``.radius_count`` / ``.mean_knn_distance`` (kernels ``k_knn_query_pyramid``, ``k_knn_query_topk``, ``k_radius_count``).
+  * ``CloudIndex(xyz)``: the Morton grid and octree of csrc/knn.hip (``neighbours.PointGrid`` / ``PointPyramid``) built once;
+    ``.knn`` / ``.radius_count`` / ``.mean_knn_distance`` (kernels ``k_knn_query_pyramid``, ``k_radius_count``).
   * ``voxel_downsample``: one point per occupied voxel, the mean (or the input point nearest the mean) of every attribute
     (csrc/cloud.hip ``k_voxel_reduce``: fp64 sums in a fixed order, no atomics, bitwise repeatable).
   * ``radius_outlier_mask`` / ``statistical_outlier_mask``.
@@ -15,12 +15,8 @@ import torch
 
 from . import ops
 from ._lib import call, ptr, require_gpu, stream
-from .ext.sdfgen import _MAX_ROUNDS, _grid_args
-from .normals import PointGrid, PointPyramid, choose_cell_size
+from .neighbours import MAX_K, _RINGS, PointGrid, PointPyramid, _grid_args, choose_cell_size, search_every_scale
 from .svh import inv_w0_f32
-
-MAX_K = 32              # csrc/knn.hip keeps the candidates of a query sorted in registers
-_RINGS = 4              # rings searched per octree level / per grid (ext/sdfgen.py)
 
 
 def _check_points(xyz, cell, what='xyz'):
@@ -97,46 +93,34 @@ class CloudIndex:
         else:
             q = self._queries(query, pg.cell)
             nq = q.shape[0]
-        idx = torch.zeros((nq, k), dtype=torch.int32, device=dev)        # (zeroed: a row the search hands back is not written)
-        d2 = torch.zeros((nq, k), dtype=torch.float32, device=dev)
-        valid = torch.empty(nq, dtype=torch.int32, device=dev)
-        call('nksr_knn_query_pyramid', self.pyramid.struct, self.n, ptr(q), nq, k, int(ex), None, _RINGS, ptr(idx), ptr(d2), ptr(valid),
-             stream())
-        ok = valid > 0
         out_idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
-        if query is None:               # rows are in sorted order: back to the caller's
-            out_idx[pg.perm] = pg.perm[idx.long()]
-            out_d2 = torch.empty_like(d2)
-            out_d2[pg.perm] = d2
-            okc = torch.empty_like(ok)
-            okc[pg.perm] = ok
-            ok = okc
-        else:
-            out_idx[:] = pg.perm[idx.long()]
-            out_d2 = d2
-        todo = torch.nonzero(~ok).flatten()
-        # what the octree hands back (farther from the cloud than its top level reaches): single grids, 4x coarser per round
-        cell = self.pyramid.top_cell * 2.0
-        for _ in range(_MAX_ROUNDS):
-            if not todo.numel():
-                break
-            g = PointGrid(self.xyz, cell)
-            m = todo.numel()
-            qs = (self.xyz[todo] if query is None else q[todo]).contiguous()
-            me = self._ranks(g)[todo].contiguous() if ex else None
-            i2 = torch.empty((m, k), dtype=torch.int32, device=dev)
-            s2 = torch.empty((m, k), dtype=torch.float32, device=dev)
-            v2 = torch.empty(m, dtype=torch.int32, device=dev)
-            call('nksr_knn_query', ptr(g.xyz), self.n, *_grid_args(g), ptr(qs), m, k, int(ex), ptr(me), _RINGS, ptr(i2), ptr(s2), ptr(v2),
-                 stream())
-            good = v2 > 0
-            rows = todo[good]
-            out_idx[rows] = g.perm[i2[good].long()]
-            out_d2[rows] = s2[good]
-            todo = todo[~good]
-            cell *= 4.0
-        if todo.numel():
-            raise RuntimeError('knn: %d queries found no %d neighbours' % (todo.numel(), k))
+        out_d2 = torch.empty((nq, k), dtype=torch.float32, device=dev)
+
+        def run(index, rows):
+            g, full = index.pg, rows is None
+            if full:                        # every row; a self-query runs in the grid's order (query NULL) and goes back to the caller's
+                qs, me, m = q, None, nq
+                rows = g.perm if query is None else slice(None)
+            else:
+                qs = (self.xyz if query is None else q)[rows].contiguous()
+                me = self._ranks(g)[rows].contiguous() if ex else None
+                m = rows.numel()
+            idx = torch.zeros((m, k), dtype=torch.int32, device=dev)         # (zeroed: a row the search hands back is not written)
+            d2 = torch.zeros((m, k), dtype=torch.float32, device=dev)
+            valid = torch.empty(m, dtype=torch.int32, device=dev)
+            call('nksr_knn_query_pyramid', index.struct, self.n, ptr(qs), m, k, int(ex), ptr(me), _RINGS, ptr(idx), ptr(d2), ptr(valid), stream())
+            good = valid > 0
+            if full:                        # all rows at once: written through, the rows handed back are overwritten later
+                out_idx[rows] = g.perm[idx.long()]
+                out_d2[rows] = d2
+                ok = torch.empty_like(good)
+                ok[rows] = good
+                return ok
+            out_idx[rows[good]] = g.perm[idx[good].long()]
+            out_d2[rows[good]] = d2[good]
+            return good
+
+        search_every_scale(self.xyz, self.pyramid, run, k, nq, None, 'knn: %%d queries found no %d neighbours' % k)
         return out_idx, torch.sqrt(out_d2)
 
     def mean_knn_distance(self, k):

@@ -7,9 +7,11 @@
 //   k_sdf_pyramid      signed distance of arbitrary queries to an oriented cloud from their k nearest reference points -- the
 //                      training ground truth ext.sdfgen.sdf_from_points (ext/sdfgen/sdf_from_points.cu:32-140 on top of the
 //                      kd-tree of ext/common/kdtree_cuda.cu; call sites models/loss.py:85, dataset/av_gt_geometry.py:72):
-//                      sign vote or IMLS; k_knn_mean_dist_pyramid = its adaptive_knn radius.  k <= 32:
-//                      candidates sorted in registers, an octree over the grid searched in one launch (second half of this file);
-//                      k_sdf_from_points / k_knn_mean_dist = the same on ONE grid by bisection (any k; what the host falls back to)
+//                      sign vote or IMLS; k_knn_mean_dist_pyramid = its adaptive_knn radius;
+//                      k_knn_query_pyramid = the neighbours themselves written out (nksr_amd/cloud.py).  k <= 32: candidates sorted in
+//                      registers, an octree over the grid searched in one launch (second half of this file) -- at EVERY scale: a single
+//                      grid is the octree with one level.  k_sdf_from_points / k_knn_mean_dist = the any-k path: ONE grid, bisection
+//                      (the host sends them k > 32 only)
 // The cloud is Morton-sorted by a uniform grid (cell size chosen by the host so that a 3^3 block
 // holds a few times k points); cells are contiguous point ranges found through the voxel hash.
 // EXACT selection without a per-thread heap: the k-th smallest squared distance is found by a
@@ -662,17 +664,6 @@ __device__ __forceinline__ int knn_rings(float cellsz, const float q[3], const i
         visit(c[0] + ox, c[1] + oy, c[2] + oz);
     }
 }
-// one grid: the k nearest reference points of q; false: fewer than k inside max_ring rings
-template <int KMAX>
-__device__ __forceinline__ bool knn_topk(const KnnGrid& g, const float q[3], int k, int max_ring, TopK<KMAX>& top) {
-    int c[3];
-    cell_of(g, q, c);
-    return knn_rings<KMAX>(g.cell, q, c, k, max_ring, false, top, [&](int cx, int cy, int cz) {
-        const int ci = hash_find(g.hkeys, g.hvals, g.hcap, morton_biased(cx, cy, cz, NKSR_BIAS0));
-        if (ci < 0) return;
-        knn_scan<KMAX>(g.xyz, g.start[ci], g.end[ci], q, top);
-    }) == 1;
-}
 
 // the two estimators over the k nearest neighbours in `top` (nearest first)
 template <int KMAX>
@@ -726,19 +717,6 @@ __device__ __forceinline__ void sdf_estimate(const float* __restrict__ xyz, cons
     }
     sdf[i] = out;
     if (grad) { grad[i * 3] = gr[0]; grad[i * 3 + 1] = gr[1]; grad[i * 3 + 2] = gr[2]; }
-}
-
-template <int KMAX>
-__global__ void __launch_bounds__(128) k_sdf_topk(KnnGrid g, const float* __restrict__ nrm, const float* __restrict__ ref_std,
-                                                  const float* __restrict__ query, int64_t nq, int k, int max_ring, float stdv, int imls,
-                                                  float* __restrict__ sdf, float* __restrict__ grad, int32_t* __restrict__ valid) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nq) return;
-    const float q[3] = {query[i * 3], query[i * 3 + 1], query[i * 3 + 2]};
-    TopK<KMAX> top;
-    if (!knn_topk<KMAX>(g, q, k, max_ring, top)) { valid[i] = 0; return; }
-    valid[i] = 1;
-    sdf_estimate<KMAX>(g.xyz, nrm, ref_std, q, top, k, stdv, imls, i, sdf, grad);
 }
 
 // ---- every scale in one launch: an octree over the same Morton-sorted points ---------------------------------------------------------
@@ -862,37 +840,46 @@ __device__ __forceinline__ bool knn_topk_pyramid(const KnnPyramid& P, const floa
     }
     return false;
 }
-template <int KMAX>
-__global__ void __launch_bounds__(KNN_PYR_BLOCK) k_sdf_pyramid(KnnPyramid Parg, const float* __restrict__ nrm, const float* __restrict__ ref_std,
-                                                               const float* __restrict__ query, int64_t nq, int k, int max_ring, float stdv,
-                                                               int imls, float* __restrict__ sdf, float* __restrict__ grad,
-                                                               int32_t* __restrict__ valid) {
+// How every pyramid kernel starts: the pyramid copied from the kernel arguments into LDS (by thread 0, then a barrier: EVERY thread of the
+// workgroup must come here), and this thread's column of the descent stacks, one (node, cursor) pair per level.  Three separate LDS
+// arrays, as they were when each kernel declared its own: packed into one struct the kernels came out with other register counts.
+__device__ __forceinline__ const KnnPyramid& knn_pyramid_lds(const KnnPyramid& Parg, int*& node, unsigned char*& cursor) {
     __shared__ int s_node[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
     __shared__ unsigned char s_cursor[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
     __shared__ KnnPyramid P;
     if (threadIdx.x == 0) P = Parg;
     __syncthreads();
+    node = &s_node[0][threadIdx.x];
+    cursor = &s_cursor[0][threadIdx.x];
+    return P;
+}
+template <int KMAX>
+__global__ void __launch_bounds__(KNN_PYR_BLOCK) k_sdf_pyramid(KnnPyramid Parg, const float* __restrict__ nrm, const float* __restrict__ ref_std,
+                                                               const float* __restrict__ query, int64_t nq, int k, int max_ring, float stdv,
+                                                               int imls, float* __restrict__ sdf, float* __restrict__ grad,
+                                                               int32_t* __restrict__ valid) {
+    int* node;
+    unsigned char* cursor;
+    const KnnPyramid& P = knn_pyramid_lds(Parg, node, cursor);
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq) return;
     const float q[3] = {query[i * 3], query[i * 3 + 1], query[i * 3 + 2]};
     TopK<KMAX> top;
-    if (!knn_topk_pyramid<KMAX>(P, q, k, max_ring, top, &s_node[0][threadIdx.x], &s_cursor[0][threadIdx.x])) { valid[i] = 0; return; }
+    if (!knn_topk_pyramid<KMAX>(P, q, k, max_ring, top, node, cursor)) { valid[i] = 0; return; }
     valid[i] = 1;
     sdf_estimate<KMAX>(P.xyz, nrm, ref_std, q, top, k, stdv, imls, i, sdf, grad);
 }
 template <int KMAX>
 __global__ void __launch_bounds__(KNN_PYR_BLOCK) k_knn_mean_dist_pyramid(KnnPyramid Parg, int64_t n, int k, int max_ring, float* __restrict__ out,
                                                                          int32_t* __restrict__ valid) {
-    __shared__ int s_node[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
-    __shared__ unsigned char s_cursor[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
-    __shared__ KnnPyramid P;
-    if (threadIdx.x == 0) P = Parg;
-    __syncthreads();
+    int* node;
+    unsigned char* cursor;
+    const KnnPyramid& P = knn_pyramid_lds(Parg, node, cursor);
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float q[3] = {P.xyz[i * 3], P.xyz[i * 3 + 1], P.xyz[i * 3 + 2]};
     TopK<KMAX> top;
-    if (!knn_topk_pyramid<KMAX>(P, q, k, max_ring, top, &s_node[0][threadIdx.x], &s_cursor[0][threadIdx.x])) { valid[i] = 0; out[i] = 0.f; return; }
+    if (!knn_topk_pyramid<KMAX>(P, q, k, max_ring, top, node, cursor)) { valid[i] = 0; out[i] = 0.f; return; }
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < KMAX; ++j)
@@ -921,22 +908,6 @@ __global__ void __launch_bounds__(256) k_pyramid_level(const int64_t* __restrict
     cmask[p] = (uint8_t)m;
     pstart[p] = cstart[lo];
     pend[p] = cend[j - 1];
-}
-
-template <int KMAX>
-__global__ void __launch_bounds__(128) k_knn_mean_dist_topk(KnnGrid g, int64_t n, int k, int max_ring, float* __restrict__ out,
-                                                            int32_t* __restrict__ valid) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float q[3] = {g.xyz[i * 3], g.xyz[i * 3 + 1], g.xyz[i * 3 + 2]};
-    TopK<KMAX> top;
-    if (!knn_topk<KMAX>(g, q, k, max_ring, top)) { valid[i] = 0; out[i] = 0.f; return; }
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j)
-        if (j >= KMAX - k) s += sqrtf(top.d2[j]);
-    out[i] = s / (float)k;
-    valid[i] = 1;
 }
 
 static KnnGrid make_grid(const float* xyz_sorted, const int32_t* start, const int32_t* end, const int64_t* hkeys,
@@ -987,19 +958,23 @@ extern "C" int nksr_sdf_from_points(const float* xyz_sorted, const float* normal
     if (!(stdv > 0.f)) return nksr_set_error(NKSR_ERR_ARG, "stdv must be > 0");
     if (!xyz_sorted || !normal_sorted || !query || !sdf_out || !valid_out) return nksr_set_error(NKSR_ERR_ARG, "NULL arrays");
     KnnGrid g = make_grid(xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell);
-    const dim3 gr(nksr_blocks(nq, 128)), bl(128);
-#define SDF_TOPK(KM) hipLaunchKernelGGL((k_sdf_topk<KM>), gr, bl, 0, (hipStream_t)stream, g, normal_sorted, ref_std_sorted, query, nq, k, max_ring, stdv, imls, sdf_out, grad_out, valid_out)
-    if (k <= 8) SDF_TOPK(8);
-    else if (k <= 16) SDF_TOPK(16);
-    else if (k <= 32) SDF_TOPK(32);
-    else                                   // more neighbours than fit the register list: the bisection kernel
-        hipLaunchKernelGGL(k_sdf_from_points, gr, bl, 0, (hipStream_t)stream, g, normal_sorted, ref_std_sorted, query,
-                           nq, k, max_ring, stdv, imls, sdf_out, grad_out, valid_out);
-#undef SDF_TOPK
+    hipLaunchKernelGGL(k_sdf_from_points, dim3(nksr_blocks(nq, 128)), dim3(128), 0, (hipStream_t)stream, g, normal_sorted, ref_std_sorted, query,
+                       nq, k, max_ring, stdv, imls, sdf_out, grad_out, valid_out);
     NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
 
+// The pyramid kernels are templates over the size of the register list: KERNEL<8 / 16 / 32 / KLAST> for `slots` <= 8 / 16 / 32 / more
+// (KLAST = 32 where the entry point admits no more than 32), one thread per row, on `stream` of the calling function.
+#define KNN_PYR_LAUNCH(KERNEL, KM, rows, ...) \
+    hipLaunchKernelGGL((KERNEL<KM>), dim3(nksr_blocks(rows, KNN_PYR_BLOCK)), dim3(KNN_PYR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__)
+#define KNN_PYR_DISPATCH(KERNEL, KLAST, slots, rows, ...)                  \
+    do {                                                                   \
+        if ((slots) <= 8) KNN_PYR_LAUNCH(KERNEL, 8, rows, __VA_ARGS__);    \
+        else if ((slots) <= 16) KNN_PYR_LAUNCH(KERNEL, 16, rows, __VA_ARGS__); \
+        else if ((slots) <= 32) KNN_PYR_LAUNCH(KERNEL, 32, rows, __VA_ARGS__); \
+        else KNN_PYR_LAUNCH(KERNEL, KLAST, rows, __VA_ARGS__);             \
+    } while (0)
 static int make_pyramid(KnnPyramid& P, const nksr_knn_pyramid_t* p) {
     if (!p || p->levels < 1 || p->levels > NKSR_KNN_LEVELS || !p->xyz_sorted) return nksr_set_error(NKSR_ERR_ARG, "kNN pyramid: 1..%d levels", NKSR_KNN_LEVELS);
     memset(&P, 0, sizeof(P));
@@ -1032,12 +1007,7 @@ extern "C" int nksr_sdf_from_points_pyramid(const nksr_knn_pyramid_t* pyramid, c
     if (!normal_sorted || !query || !sdf_out || !valid_out) return nksr_set_error(NKSR_ERR_ARG, "NULL arrays");
     KnnPyramid P;
     if (int rc = make_pyramid(P, pyramid)) return rc;
-    const dim3 gr(nksr_blocks(nq, 128)), bl(128);
-#define SDF_PYR(KM) hipLaunchKernelGGL((k_sdf_pyramid<KM>), gr, bl, 0, (hipStream_t)stream, P, normal_sorted, ref_std_sorted, query, nq, k, max_ring, stdv, imls, sdf_out, grad_out, valid_out)
-    if (k <= 8) SDF_PYR(8);
-    else if (k <= 16) SDF_PYR(16);
-    else SDF_PYR(32);
-#undef SDF_PYR
+    KNN_PYR_DISPATCH(k_sdf_pyramid, 32, k, nq, P, normal_sorted, ref_std_sorted, query, nq, k, max_ring, stdv, imls, sdf_out, grad_out, valid_out);
     NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
@@ -1046,10 +1016,7 @@ extern "C" int nksr_knn_mean_dist_pyramid(const nksr_knn_pyramid_t* pyramid, int
     if (k < 1 || k > 32) return nksr_set_error(NKSR_ERR_ARG, "pyramid search: 1 <= k <= 32 (got %d)", k);
     KnnPyramid P;
     if (int rc = make_pyramid(P, pyramid)) return rc;
-    const dim3 gr(nksr_blocks(n, 128)), bl(128);
-    if (k <= 8) hipLaunchKernelGGL((k_knn_mean_dist_pyramid<8>), gr, bl, 0, (hipStream_t)stream, P, n, k, max_ring, out, valid_out);
-    else if (k <= 16) hipLaunchKernelGGL((k_knn_mean_dist_pyramid<16>), gr, bl, 0, (hipStream_t)stream, P, n, k, max_ring, out, valid_out);
-    else hipLaunchKernelGGL((k_knn_mean_dist_pyramid<32>), gr, bl, 0, (hipStream_t)stream, P, n, k, max_ring, out, valid_out);
+    KNN_PYR_DISPATCH(k_knn_mean_dist_pyramid, 32, k, n, P, n, k, max_ring, out, valid_out);
     NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
@@ -1060,11 +1027,7 @@ extern "C" int nksr_knn_mean_dist(const float* xyz_sorted, int64_t n, const int3
     if (n <= 0) return NKSR_OK;
     if (k < 1) return nksr_set_error(NKSR_ERR_ARG, "k must be >= 1");
     KnnGrid g = make_grid(xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell);
-    const dim3 gr(nksr_blocks(n, 128)), bl(128);
-    if (k <= 8) hipLaunchKernelGGL((k_knn_mean_dist_topk<8>), gr, bl, 0, (hipStream_t)stream, g, n, k, max_ring, out, valid_out);
-    else if (k <= 16) hipLaunchKernelGGL((k_knn_mean_dist_topk<16>), gr, bl, 0, (hipStream_t)stream, g, n, k, max_ring, out, valid_out);
-    else if (k <= 32) hipLaunchKernelGGL((k_knn_mean_dist_topk<32>), gr, bl, 0, (hipStream_t)stream, g, n, k, max_ring, out, valid_out);
-    else hipLaunchKernelGGL(k_knn_mean_dist, gr, bl, 0, (hipStream_t)stream, g, n, k, max_ring, out, valid_out);
+    hipLaunchKernelGGL(k_knn_mean_dist, dim3(nksr_blocks(n, 128)), dim3(128), 0, (hipStream_t)stream, g, n, k, max_ring, out, valid_out);
     NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
@@ -1113,20 +1076,16 @@ __global__ void __launch_bounds__(NKSR_NN_BLOCK) k_nn_metrics(KnnPyramid Parg, c
                                                               const float* __restrict__ qnrm, int64_t nq, int max_ring, float* __restrict__ dist,
                                                               float* __restrict__ dot, double* __restrict__ partials) {
     static_assert(NKSR_NN_BLOCK == KNN_PYR_BLOCK, "one LDS slot row per thread");
-    __shared__ int s_node[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
-    __shared__ unsigned char s_cursor[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
-    __shared__ KnnPyramid P;
     __shared__ double s_red[NKSR_METRIC_FIELDS][NKSR_NN_BLOCK];
-    if (threadIdx.x == 0) P = Parg;
-    __syncthreads();
+    int* node;
+    unsigned char* cursor;
+    const KnnPyramid& P = knn_pyramid_lds(Parg, node, cursor);
     const int64_t i = (int64_t)blockIdx.x * NKSR_NN_BLOCK + threadIdx.x;
     double acc[NKSR_METRIC_FIELDS];
 #pragma unroll
     for (int f = 0; f < NKSR_METRIC_FIELDS; ++f) acc[f] = 0.0;
     if (i < nq) {
         const float q[3] = {query[i * 3], query[i * 3 + 1], query[i * 3 + 2]};
-        int* node = &s_node[0][threadIdx.x];
-        unsigned char* cursor = &s_cursor[0][threadIdx.x];
         TopK<1> top;
         const float lim = (float)(NKSR_BIAS0 >> 1);           // cell indices well inside the biased key range
         const bool in_range = fabsf(q[0] * P.inv_cell) < lim && fabsf(q[1] * P.inv_cell) < lim && fabsf(q[2] * P.inv_cell) < lim;
@@ -1182,7 +1141,7 @@ extern "C" int nksr_nn_metrics(const nksr_knn_pyramid_t* pyramid, const int64_t*
 }
 
 // ---- the k nearest WRITTEN OUT, and the points within a radius counted (nksr_amd/cloud.py) ---------------------------------------------
-// The searches are the ones above (knn_topk_pyramid / knn_topk, one thread per query, the block shape and LDS stacks of k_sdf_pyramid);
+// The search is the one above (knn_topk_pyramid, one thread per query, the block shape and LDS stacks of k_sdf_pyramid);
 // the new work is the stores.  exclude_self: the list is searched with one slot more (kk = k + 1) and the query's own point dropped
 // from it on the way out -- it is the nearest candidate or tied with it at distance 0, so it is in the list unless kk OTHER points
 // lie at distance 0 too, and then the first k of the list are k nearest others all the same.  Points that merely share the
@@ -1208,32 +1167,16 @@ __global__ void __launch_bounds__(KNN_PYR_BLOCK) k_knn_query_pyramid(KnnPyramid 
                                                                      const int32_t* __restrict__ self_index, int max_ring,
                                                                      int32_t* __restrict__ idx_out, float* __restrict__ d2_out,
                                                                      int32_t* __restrict__ valid) {
-    __shared__ int s_node[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
-    __shared__ unsigned char s_cursor[NKSR_KNN_LEVELS][KNN_PYR_BLOCK];
-    __shared__ KnnPyramid P;
-    if (threadIdx.x == 0) P = Parg;
-    __syncthreads();
+    int* node;
+    unsigned char* cursor;
+    const KnnPyramid& P = knn_pyramid_lds(Parg, node, cursor);
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq) return;
     const float* qp = query ? query + i * 3 : P.xyz + i * 3;
     const float q[3] = {qp[0], qp[1], qp[2]};
     const int kk = k + (exclude_self ? 1 : 0);
     TopK<KMAX> top;
-    if (!knn_topk_pyramid<KMAX>(P, q, kk, max_ring, top, &s_node[0][threadIdx.x], &s_cursor[0][threadIdx.x])) { valid[i] = 0; return; }
-    valid[i] = 1;
-    knn_write<KMAX>(top, kk, k, exclude_self ? (self_index ? self_index[i] : (int)i) : -1, i, idx_out, d2_out);
-}
-template <int KMAX>
-__global__ void __launch_bounds__(128) k_knn_query_topk(KnnGrid g, const float* __restrict__ query, int64_t nq, int k, int exclude_self,
-                                                        const int32_t* __restrict__ self_index, int max_ring, int32_t* __restrict__ idx_out,
-                                                        float* __restrict__ d2_out, int32_t* __restrict__ valid) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nq) return;
-    const float* qp = query ? query + i * 3 : g.xyz + i * 3;
-    const float q[3] = {qp[0], qp[1], qp[2]};
-    const int kk = k + (exclude_self ? 1 : 0);
-    TopK<KMAX> top;
-    if (!knn_topk<KMAX>(g, q, kk, max_ring, top)) { valid[i] = 0; return; }
+    if (!knn_topk_pyramid<KMAX>(P, q, kk, max_ring, top, node, cursor)) { valid[i] = 0; return; }
     valid[i] = 1;
     knn_write<KMAX>(top, kk, k, exclude_self ? (self_index ? self_index[i] : (int)i) : -1, i, idx_out, d2_out);
 }
@@ -1284,14 +1227,8 @@ extern "C" int nksr_knn_query_pyramid(const nksr_knn_pyramid_t* pyramid, int64_t
     KnnPyramid P;
     if (int rc = make_pyramid(P, pyramid)) return rc;
     if (nq == 0) return NKSR_OK;
-    const dim3 gr(nksr_blocks(nq, KNN_PYR_BLOCK)), bl(KNN_PYR_BLOCK);
-    const int kk = k + (exclude_self ? 1 : 0);
-#define KNN_Q(KM) hipLaunchKernelGGL((k_knn_query_pyramid<KM>), gr, bl, 0, (hipStream_t)stream, P, query, nq, k, exclude_self, self_index, max_ring, idx_out, dist2_out, valid_out)
-    if (kk <= 8) KNN_Q(8);
-    else if (kk <= 16) KNN_Q(16);
-    else if (kk <= 32) KNN_Q(32);
-    else KNN_Q(33);
-#undef KNN_Q
+    KNN_PYR_DISPATCH(k_knn_query_pyramid, 33, k + (exclude_self ? 1 : 0), nq, P, query, nq, k, exclude_self, self_index, max_ring, idx_out, dist2_out,
+                     valid_out);
     NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
@@ -1300,24 +1237,6 @@ static int knn_grid_args(const char* who, const float* xyz_sorted, const int32_t
     if (!xyz_sorted || !start || !end || !hkeys || !hvals) return nksr_set_error(NKSR_ERR_ARG, "%s: NULL grid arrays", who);
     if (hcap < 8 || (hcap & (hcap - 1))) return nksr_set_error(NKSR_ERR_ARG, "%s: hcap must be a power of two >= 8 (got %d)", who, hcap);
     if (!(cell > 0.f) || !(inv_cell > 0.f)) return nksr_set_error(NKSR_ERR_ARG, "%s: cell and inv_cell must be > 0", who);
-    return NKSR_OK;
-}
-extern "C" int nksr_knn_query(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,
-                              const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* query, int64_t nq, int k, int exclude_self,
-                              const int32_t* self_index, int max_ring, int32_t* idx_out, float* dist2_out, int32_t* valid_out, void* stream) {
-    if (int rc = knn_query_args("knn query", n_ref, query, nq, k, exclude_self, max_ring, idx_out, dist2_out, valid_out)) return rc;
-    if (int rc = knn_grid_args("knn query", xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell)) return rc;
-    if (nq == 0) return NKSR_OK;
-    KnnGrid g = make_grid(xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell);
-    const dim3 gr(nksr_blocks(nq, 128)), bl(128);
-    const int kk = k + (exclude_self ? 1 : 0);
-#define KNN_Q(KM) hipLaunchKernelGGL((k_knn_query_topk<KM>), gr, bl, 0, (hipStream_t)stream, g, query, nq, k, exclude_self, self_index, max_ring, idx_out, dist2_out, valid_out)
-    if (kk <= 8) KNN_Q(8);
-    else if (kk <= 16) KNN_Q(16);
-    else if (kk <= 32) KNN_Q(32);
-    else KNN_Q(33);
-#undef KNN_Q
-    NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
 extern "C" int nksr_radius_count(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,

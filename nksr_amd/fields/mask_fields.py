@@ -79,7 +79,7 @@ class PCNNField(BaseField):
 
     def evaluate_color(self, xyz_world):
         """Colour of the nearest input point (grid-hash nearest neighbour, csrc/knn.hip)."""
-        from ..normals import PointGrid, choose_cell_size
+        from ..neighbours import PointGrid, choose_cell_size
         if getattr(self, '_grid', None) is None or self._grid.xyz.device != xyz_world.device:
             ref = self.xyz.to(xyz_world.device)
             self._grid = PointGrid(ref, choose_cell_size(ref, 8))

@@ -20,7 +20,7 @@ from ._lib import METRIC_FIELDS, NN_BLOCK, call, ptr, require_gpu, stream, with_
 from .density import bbox_center
 from .mesh_query import MeshQuery, mesh_occupancy  # noqa: F401  (re-exported: nksr.metrics.MeshQuery)
 from .mesh_topology import MeshTopology  # noqa: F401  (re-exported: nksr.metrics.MeshTopology)
-from .normals import PointGrid, PointPyramid, choose_cell_size
+from .neighbours import PointGrid, PointPyramid, choose_cell_size
 
 THRESHOLDS = (0.01, 0.015, 0.02, 0.002, 0.1)    # NKSR_METRIC_THRESHOLDS; 'f-score' at [0], '-15' [1], '-20' [2], '-outdoor' [4]
 MAX_RING = 4                                    # rings per pyramid level before a query climbs (nksr_nn_metrics)

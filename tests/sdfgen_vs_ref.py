@@ -65,7 +65,7 @@ def main():
                 print('| %d | %d | %s | (no oracle/_ref) | %s | | |' % (n_ref, n_q, mode, cols))
     if '--breakdown' in sys.argv:
         from nksr_amd._lib import call, ptr, stream
-        from nksr_amd.normals import PointGrid, PointPyramid, choose_cell_size
+        from nksr_amd.neighbours import PointGrid, PointPyramid, choose_cell_size
         print()
         print('| reference points = queries | cell size ms | grid ms | octree levels | octree ms | search + estimator kernel ms | whole call ms |')
         print('|---|---|---|---|---|---|---|')

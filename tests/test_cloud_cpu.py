@@ -97,30 +97,27 @@ def test_cloud_c_abi_argument_errors_without_a_gpu():
     i64, i32, ci, cf = C.c_int64, C.c_int32, C.c_int, C.c_float
     grid = (ints, ints, longs, ints, i32(8), cf(1.0), cf(1.0))
 
-    def knn_query(xyz=one, n_ref=10, g=grid, query=one, nq=1, k=4, ex=0, rings=4, idx=ints, d2=one, valid=ints):
-        return lib.nksr_knn_query(xyz, i64(n_ref), *g, query, i64(nq), ci(k), ci(ex), null, ci(rings), idx, d2, valid, null)
-    assert knn_query(k=33) != 0 and '<= 32' in err()
-    assert knn_query(k=0) != 0 and '<= 32' in err()
-    assert knn_query(k=10, ex=1) != 0 and 'reference points' in err()
-    assert knn_query(nq=-1) != 0 and 'negative' in err()
-    assert knn_query(rings=0) != 0 and 'max_ring' in err()
-    assert knn_query(idx=null) != 0 and 'NULL' in err()
-    assert knn_query(xyz=null) != 0 and 'NULL' in err()
-    assert knn_query(query=null, nq=11) != 0 and 'n_ref' in err()
-    assert knn_query(g=(ints, ints, longs, ints, i32(12), cf(1.0), cf(1.0))) != 0 and 'power of two' in err()
-    assert knn_query(g=(ints, ints, longs, ints, i32(8), cf(0.0), cf(1.0))) != 0 and 'cell' in err()
-    assert knn_query(nq=0) == 0
+    pyr = _lib.KnnPyramidT()                  # one level, complete: the checks on the other arguments are reached
+    pyr.xyz_sorted = C.cast(one, C.c_void_p)
+    pyr.start[0], pyr.end[0], pyr.hvals[0] = (C.cast(ints, C.c_void_p),) * 3
+    pyr.hkeys[0], pyr.hcap[0], pyr.levels, pyr.cell, pyr.inv_cell = C.cast(longs, C.c_void_p), 8, 1, 1.0, 1.0
 
-    pyr = _lib.KnnPyramidT()
-
-    def knn_pyr(p=pyr, n_ref=10, nq=1, k=4, ex=0, valid=ints):
-        return lib.nksr_knn_query_pyramid(C.byref(p) if p is not None else None, i64(n_ref), one, i64(nq), ci(k), ci(ex), null, ci(4), ints, one,
-                                          valid, null)
+    def knn_pyr(p=pyr, n_ref=10, query=one, nq=1, k=4, ex=0, rings=4, idx=ints, d2=one, valid=ints):
+        return lib.nksr_knn_query_pyramid(C.byref(p) if p is not None else None, i64(n_ref), query, i64(nq), ci(k), ci(ex), null, ci(rings), idx,
+                                          d2, valid, null)
+    assert knn_pyr(k=33) != 0 and '<= 32' in err()
     assert knn_pyr(k=40) != 0 and '<= 32' in err()
+    assert knn_pyr(k=0) != 0 and '<= 32' in err()
+    assert knn_pyr(k=10, ex=1) != 0 and 'reference points' in err()
     assert knn_pyr(k=32, ex=1, n_ref=32) != 0 and 'reference points' in err()
+    assert knn_pyr(nq=-1) != 0 and 'negative' in err()
+    assert knn_pyr(rings=0) != 0 and 'max_ring' in err()
+    assert knn_pyr(idx=null) != 0 and 'NULL' in err()
     assert knn_pyr(valid=null) != 0 and 'NULL' in err()
-    assert knn_pyr() != 0 and 'pyramid' in err()                 # levels = 0
+    assert knn_pyr(query=null, nq=11) != 0 and 'n_ref' in err()
+    assert knn_pyr(p=_lib.KnnPyramidT()) != 0 and 'pyramid' in err()                 # levels = 0
     assert knn_pyr(p=None) != 0 and 'pyramid' in err()
+    assert knn_pyr(nq=0) == 0
 
     def count(xyz=one, g=grid, query=one, nq=1, n_ref=10, radius=0.5, out=ints):
         return lib.nksr_radius_count(xyz, i64(n_ref), *g, query, i64(nq), cf(radius), i32(0), ci(0), null, out, null)
@@ -129,6 +126,8 @@ def test_cloud_c_abi_argument_errors_without_a_gpu():
     assert count(radius=2.0) != 0 and '>= radius' in err()      # the grid's cell is 1
     assert count(out=null) != 0 and 'NULL' in err()
     assert count(xyz=null) != 0 and 'NULL' in err()
+    assert count(g=(ints, ints, longs, ints, i32(12), cf(1.0), cf(1.0))) != 0 and 'power of two' in err()
+    assert count(g=(ints, ints, longs, ints, i32(8), cf(0.0), cf(1.0))) != 0 and 'cell' in err()
     assert count(query=null, nq=11) != 0 and 'n_ref' in err()
     assert count(nq=0) == 0
 

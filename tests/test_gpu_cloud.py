@@ -103,6 +103,62 @@ def test_knn_far_query_takes_the_coarse_grids():
         assert (np.sort(idx.cpu().numpy()[sure], axis=1) == np.sort(ref_j[sure, :k], axis=1)).all()
 
 
+@functools.lru_cache(None)
+def _dup():
+    """600 random points with 40 exact copies among them, 200 queries near the cloud, and the CloudIndex over the points"""
+    from nksr_amd import cloud
+    rs = np.random.RandomState(11)
+    x = rs.rand(600, 3).astype(np.float32)
+    x = np.concatenate([x, x[rs.randint(0, 600, 40)]])
+    q = (x[rs.randint(0, 640, 200)] + 0.05 * rs.randn(200, 3)).astype(np.float32)
+    return x, q, cloud.CloudIndex(_gpu(x))
+
+
+@pytest.mark.parametrize('mode,k', [(m, k) for m in ('query', 'self') for k in (1, 8, 9, 17, 32)] + [('self_ex', 32)])
+def test_one_level_pyramid_finds_what_the_octree_finds(mode, k):
+    """nksr_knn_query_pyramid on the octree and on the same grid as a pyramid of ONE level (what the coarse rounds run): where both
+    answer, the k smallest squared distances are one multiset, computed by the same knn_d2 -- bit for bit equal.  Both against an fp64
+    brute force at the 1e-5 relative tolerance of this file; self_ex at k = 32 is the 33-slot list."""
+    from nksr_amd._lib import call, ptr, stream
+    from nksr_amd.neighbours import PointPyramid
+    x, q, ci = _dup()
+    pg, ex = ci.pg, mode == 'self_ex'
+    one = PointPyramid(pg, max_levels=1)
+    assert one.levels == 1 and one.struct.levels == 1 and ci.pyramid.levels > 1
+    qg = _gpu(q) if mode == 'query' else None
+    qs = qg if mode == 'query' else pg.xyz                 # (a self-query runs in the grid's order)
+    nq = qs.shape[0]
+
+    def run(pyr):
+        idx = torch.zeros((nq, k), dtype=torch.int32, device=DEV)
+        d2 = torch.zeros((nq, k), dtype=torch.float32, device=DEV)
+        valid = torch.zeros(nq, dtype=torch.int32, device=DEV)
+        call('nksr_knn_query_pyramid', pyr.struct, ci.n, ptr(qg), nq, k, int(ex), None, 4, ptr(idx), ptr(d2), ptr(valid), stream())
+        return idx.long(), d2, valid > 0
+    ia, da, va = run(ci.pyramid)
+    ib, db, vb = run(one)
+    both = va & vb
+    print('%s k=%d  valid: octree %d, one level %d of %d' % (mode, k, int(va.sum()), int(vb.sum()), nq))
+    assert int(both.sum()) >= nq // 2
+    assert torch.equal(da[both], db[both])
+    exact = 'donot_use_mm_for_euclid_dist'                 # (the matrix-product form leaves ~1e-8 where two points coincide)
+    full = torch.cdist(qs.double(), pg.xyz.double(), compute_mode=exact)
+    if ex:
+        full.fill_diagonal_(float('inf'))
+    ref = full.topk(k, dim=1, largest=False).values
+    for idx, d2, v in ((ia, da, va), (ib, db, vb)):
+        torch.testing.assert_close(d2[v].double().sqrt(), ref[v], rtol=1e-5, atol=0)
+        torch.testing.assert_close(torch.gather(full, 1, idx)[v], ref[v], rtol=1e-5, atol=0)    # the indices name points at those distances
+    # a row the single level does not reach is answered by the rounds: knn() raises if one is left, and agrees with the brute force
+    idx, dist = ci.knn(k, query=qg, exclude_self=ex)
+    back = torch.cdist((qg if mode == 'query' else ci.xyz).double(), ci.xyz.double(), compute_mode=exact)
+    if ex:
+        back.fill_diagonal_(float('inf'))
+    ref = back.topk(k, dim=1, largest=False).values
+    torch.testing.assert_close(dist.double(), ref, rtol=1e-5, atol=0)
+    torch.testing.assert_close(torch.gather(back, 1, idx), ref, rtol=1e-5, atol=0)
+
+
 @pytest.mark.parametrize('k', [8, 32])
 def test_knn_duplicates_stay_when_the_point_itself_is_excluded(k):
     from nksr_amd import cloud

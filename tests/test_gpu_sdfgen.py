@@ -123,6 +123,35 @@ def test_octree_search_equals_the_single_grid_rounds_and_hands_on_what_it_cannot
         assert ((a[1] - b[1]).abs().amax(1).cpu().numpy() > 1e-4).mean() <= 2e-3
 
 
+@pytest.mark.parametrize('imls', [False, True])
+def test_more_neighbours_than_the_register_list_take_the_bisection_kernels(imls):
+    """nb_points = 40 > 32: the any-k path (csrc/knn.hip k_sdf_from_points on plain grids, coarser per round) against the oracle, at the
+    caps of the tests above.  Queries on two shells 0.15 either side of the surface (every one of the 40 neighbours votes the same
+    sign) and 30 at 100 cloud diameters, which only the coarse rounds reach."""
+    from oracle import sdfgen as osdf
+    import ext
+    dev = torch.device('cuda:0')
+    xyz, nrm = _cloud(3000)
+    rs = np.random.RandomState(7)
+
+    def shell(r, m):
+        v = rs.randn(m, 3)
+        return v / np.linalg.norm(v, axis=1, keepdims=True) * r
+    q = np.concatenate([shell(0.35, 1000), shell(0.65, 1000), shell(100.0, 30)]).astype(np.float32)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    out = ext.sdfgen.sdf_from_points(t(q), t(xyz), t(nrm), nb_points=40, stdv=0.05, compute_grad=True, imls=imls)
+    ref_s, ref_g = osdf.sdf_from_points(q, xyz, nrm, 40, 0.05, compute_grad=True, imls=imls)
+    s, g = out[0].cpu().numpy(), out[1].cpu().numpy()
+    diff = np.abs(s - ref_s)
+    bad = diff > 1e-5 + 1e-5 * np.abs(ref_s)
+    gd = np.abs(g - ref_g).max(1)
+    pu.report('sdfgen any-k[%s]' % ('imls' if imls else 'vote'), max_abs_err=float(diff[~bad].max()), flipped=int(bad.sum()),
+              grad_above_bound=int((gd[~bad] > 1e-4).sum()), queries=len(q))
+    assert bad.mean() <= 2e-3, int(bad.sum())
+    assert (gd[~bad] <= 1e-4).mean() >= 0.998
+    assert (s[:1000] < 0).all() and (s[1000:] > 0).all()
+
+
 def test_sdf_from_points_argument_errors():
     import ext
     dev = torch.device('cuda:0')
