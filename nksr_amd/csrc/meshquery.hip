@@ -6,15 +6,12 @@
 //   k_mesh_closest    exact closest point: nearer child first, boxes pruned by squared distance
 // Layouts and the predicate: include/nksr_hip.h (mesh queries) and DESIGN.md section 3.9.
 #include "common.h"
+#include "mesh_dev.h"
 
 #define BVH_BLOCK 64            // one wavefront per workgroup: the traversal stack is a per-lane column of LDS
 #define BVH_LEAF_FLAG(k) (~(int32_t)(k))
 
 __constant__ float c_bvh_dirs[NKSR_BVH_MAX_RAYS][3] = NKSR_BVH_RAY_DIRS;
-
-__device__ __forceinline__ int64_t mq_face_index(const void* faces, int is64, int64_t k) {
-    return is64 ? ((const int64_t*)faces)[k] : (int64_t)((const int32_t*)faces)[k];
-}
 
 // ---- build ------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t mq_quantise(float x, float lo, float scale) {
@@ -31,7 +28,7 @@ __global__ void __launch_bounds__(256) k_bvh_morton(const float* __restrict__ xy
     float p[3] = {0.f, 0.f, 0.f};
     if (faces) {
         for (int c = 0; c < 3; ++c) {
-            const int64_t vi = mq_face_index(faces, is64, i * 3 + c);
+            const int64_t vi = mesh_face_index(faces, is64, i * 3 + c);
             if (vi < 0 || vi >= nv) { p[0] = p[1] = p[2] = 0.f; break; }
             p[0] += xyz[vi * 3] * (1.f / 3.f);
             p[1] += xyz[vi * 3 + 1] * (1.f / 3.f);
@@ -113,7 +110,7 @@ __global__ void __launch_bounds__(256) k_bvh_refit(const float* __restrict__ v, 
     bool ok = true;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        int64_t vi = mq_face_index(faces, is64, face * 3 + c);
+        int64_t vi = mesh_face_index(faces, is64, face * 3 + c);
         if (vi < 0 || vi >= nv) { ok = false; vi = 0; }
 #pragma unroll
         for (int a = 0; a < 3; ++a) p[c][a] = v[vi * 3 + a];

@@ -7,17 +7,15 @@
 //   k_topo_*            labels of the other kind of node, per-component counts and boxes, compaction
 // Every kernel is one lane per item, latency- and atomic-bound; no sum here is a floating-point one.
 #include "common.h"
+#include "mesh_dev.h"
 
 #define TOPO_BLOCK 256
 
-__device__ __forceinline__ int64_t tp_index(const void* faces, int is64, int64_t k) {
-    return is64 ? ((const int64_t*)faces)[k] : (int64_t)((const int32_t*)faces)[k];
-}
 // the corners of face j; false for an invalid face (an index outside [0, nv), or two equal indices)
 __device__ __forceinline__ bool tp_face(const void* faces, int is64, int64_t j, int64_t nv, int64_t c[3]) {
-    c[0] = tp_index(faces, is64, j * 3);
-    c[1] = tp_index(faces, is64, j * 3 + 1);
-    c[2] = tp_index(faces, is64, j * 3 + 2);
+    c[0] = mesh_face_index(faces, is64, j * 3);
+    c[1] = mesh_face_index(faces, is64, j * 3 + 1);
+    c[2] = mesh_face_index(faces, is64, j * 3 + 2);
     return c[0] >= 0 && c[0] < nv && c[1] >= 0 && c[1] < nv && c[2] >= 0 && c[2] < nv && c[0] != c[1] && c[1] != c[2] && c[0] != c[2];
 }
 // the key no edge has and that sorts behind every edge of a mesh of nv vertices, inside the 32 + bit_length(nv) sorted bits
@@ -125,7 +123,7 @@ __global__ void __launch_bounds__(TOPO_BLOCK) k_topo_edge_table(const uint64_t* 
 __device__ __forceinline__ bool tp_forward(const void* faces, int is64, uint32_t h) {      // does half-edge h run min -> max?
     const int64_t f = h / 3u;
     const int k = (int)(h % 3u);
-    return tp_index(faces, is64, f * 3 + k) < tp_index(faces, is64, f * 3 + (k == 2 ? 0 : k + 1));
+    return mesh_face_index(faces, is64, f * 3 + k) < mesh_face_index(faces, is64, f * 3 + (k == 2 ? 0 : k + 1));
 }
 
 // totals: [0] E, [1] boundary, [2] non-manifold, [3] misoriented edges (integer atomics)
@@ -253,7 +251,7 @@ __global__ void __launch_bounds__(TOPO_BLOCK) k_topo_vertex_min_label(const void
     const int32_t l = face_label[j];
     if (l < 0) return;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) atomicMin(vertex_label + tp_index(faces, is64, j * 3 + k), l);
+    for (int k = 0; k < 3; ++k) atomicMin(vertex_label + mesh_face_index(faces, is64, j * 3 + k), l);
 }
 __global__ void __launch_bounds__(TOPO_BLOCK) k_topo_fix_unlabelled(int32_t* __restrict__ label, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * TOPO_BLOCK + threadIdx.x;
@@ -263,7 +261,7 @@ __global__ void __launch_bounds__(TOPO_BLOCK) k_topo_face_from_vertex(const void
                                                                       const int32_t* __restrict__ vertex_label, int32_t* __restrict__ face_label) {
     const int64_t j = (int64_t)blockIdx.x * TOPO_BLOCK + threadIdx.x;
     if (j >= nf) return;
-    face_label[j] = face_valid[j] ? vertex_label[tp_index(faces, is64, j * 3)] : -1;
+    face_label[j] = face_valid[j] ? vertex_label[mesh_face_index(faces, is64, j * 3)] : -1;
 }
 
 // ---- 5. per-component statistics -------------------------------------------------------------------------------------------------
@@ -295,7 +293,7 @@ __global__ void __launch_bounds__(TOPO_BLOCK) k_topo_shared_corners(const void* 
     if (l < 0) return;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int64_t v = tp_index(faces, is64, j * 3 + k);
+        const int64_t v = mesh_face_index(faces, is64, j * 3 + k);
         if (vertex_label[v] == l) continue;
         const int64_t pos = (int64_t)atomicAdd((unsigned long long*)count, 1ull);
         if (keys && pos < capacity) keys[pos] = ((uint64_t)(uint32_t)l << 32) | (uint64_t)v;     // (any order: the list is sorted next)
@@ -329,7 +327,7 @@ __global__ void __launch_bounds__(TOPO_BLOCK) k_topo_box_faces(const float* __re
     if (on) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const int64_t vi = tp_index(faces, is64, j * 3 + k);
+            const int64_t vi = mesh_face_index(faces, is64, j * 3 + k);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 const uint32_t x = tp_ordered(v[vi * 3 + a]);
@@ -384,7 +382,7 @@ __global__ void __launch_bounds__(TOPO_BLOCK) k_topo_renumber(const void* faces,
         const int64_t o = face_offsets[i];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const int32_t w = vertex_offsets[tp_index(faces, is64, i * 3 + k)];
+            const int32_t w = vertex_offsets[mesh_face_index(faces, is64, i * 3 + k)];
             if (is64) ((int64_t*)faces_out)[o * 3 + k] = w;
             else ((int32_t*)faces_out)[o * 3 + k] = w;
         }

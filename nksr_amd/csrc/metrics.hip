@@ -4,16 +4,14 @@
 //   k_metric_reduce  column sums of the per-workgroup partials of nksr_nn_metrics (knn.hip), one workgroup in a fixed order
 // The nearest-neighbour half of the evaluator is the k = 1 pyramid search of knn.hip.
 #include "common.h"
+#include "mesh_dev.h"
 
-__device__ __forceinline__ int64_t face_index(const void* faces, int is64, int64_t k) {
-    return is64 ? ((const int64_t*)faces)[k] : (int64_t)((const int32_t*)faces)[k];
-}
 // the three corners of face j in fp64; false when an index lies outside [0, nv)
 __device__ __forceinline__ bool face_corners(const float* __restrict__ v, int64_t nv, const void* faces, int is64, int64_t j, double p[3][3]) {
     bool ok = true;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        int64_t vi = face_index(faces, is64, j * 3 + c);
+        int64_t vi = mesh_face_index(faces, is64, j * 3 + c);
         if (vi < 0 || vi >= nv) { ok = false; vi = 0; }
 #pragma unroll
         for (int a = 0; a < 3; ++a) p[c][a] = (double)v[vi * 3 + a];

@@ -10,14 +10,16 @@ The tree is a linear BVH over the triangles (csrc/meshquery.hip, DESIGN.md secti
 (1, 3, 5 or 7 fixed, non-axis-aligned directions) from every query and counts every crossing with a watertight test whose signs are
 exact and whose ties on shared edges and vertices are broken per edge: on a closed mesh each ray's parity is exact, and a query is
 inside when most of its rays cross an odd number of times.  Coordinates are recentred in float64 by the centre of the mesh's bounding
-box before they are rounded to float32.  A mesh without faces has nothing inside and every distance is inf.
+box before they are rounded to float32 (nksr_amd/mesh_input.py; faces of any dtype are indices, one outside [0, V) is an error).
+A mesh without faces has nothing inside and every distance is inf.
 """
 import numpy as np
 import torch
 
-from . import ops
+from . import mesh_input, ops
 from ._lib import BVH_LEAF_FLOATS, BVH_MAX_FACES, BVH_MAX_RAYS, BVH_NODE_FLOATS, BVH_STACK, BvhT, call, ptr, stream
 from .density import bbox_center
+from .mesh_input import bbox_centre, gpu_device, is64, recentre, rows3
 
 
 def _check_rays(rays):
@@ -32,8 +34,8 @@ def morton(xyz, box, faces=None, nv=None):
     n = faces.shape[0] if faces is not None else xyz.shape[0]
     codes = torch.empty(n, dtype=torch.int64, device=xyz.device)
     index = torch.empty(n, dtype=torch.int32, device=xyz.device)
-    is64 = int(faces is not None and faces.dtype == torch.int64)
-    call('nksr_bvh_morton', ptr(xyz), xyz.shape[0] if nv is None else nv, ptr(faces), is64, n, ptr(box), ptr(codes), ptr(index), stream())
+    call('nksr_bvh_morton', ptr(xyz), xyz.shape[0] if nv is None else nv, ptr(faces), is64(faces) if faces is not None else 0, n, ptr(box),
+         ptr(codes), ptr(index), stream())
     return codes, index
 
 
@@ -65,7 +67,7 @@ def build_nodes(bvh, codes_sorted):
 def refit(bvh, v32, faces, order, parent):
     """Leaf records and every box, bottom up; bvh.depth_dev receives the depth (read by ``finish``)."""
     work = torch.empty(max(2 * (bvh.nf - 1), 1), dtype=torch.int32, device=v32.device)
-    call('nksr_bvh_refit', ptr(v32), v32.shape[0], ptr(faces), int(faces.dtype == torch.int64), ptr(order), ptr(parent), ptr(work),
+    call('nksr_bvh_refit', ptr(v32), v32.shape[0], ptr(faces), is64(faces), ptr(order), ptr(parent), ptr(work),
          bvh.struct, stream())
 
 
@@ -99,35 +101,36 @@ class MeshQuery:
     """Occupancy and distance queries against one triangle mesh (v [V, 3], f [F, 3] int32 / int64), on the GPU."""
 
     def __init__(self, v, f, device=None):
-        from .metrics import _bbox_centre, _device, _faces, _recentre, _rows3
-        if device is None and isinstance(v, torch.Tensor) and v.is_cuda:
-            device = v.device
-        dev = _device(device)
+        dev = gpu_device(device, like=v)
         vv = v if isinstance(v, torch.Tensor) else np.asarray(v)
-        _rows3(vv, 'vertices')
-        centre = _bbox_centre(vv) if vv.shape[0] else np.zeros(3)
-        v32 = _recentre(vv, centre, dev, 'vertices')
-        self._init(v32, _faces(f, v32.shape[0], dev), centre)
+        rows3(vv, 'vertices')
+        centre = bbox_centre(vv) if vv.shape[0] else np.zeros(3)
+        v32 = recentre(vv, centre, dev, 'vertices')
+        self._init(build_bvh(v32, mesh_input.faces(f, v32.shape[0], dev, cast_float=True, check_range=True)), centre)
 
     @classmethod
     def recentred(cls, v32, faces, centre):
         """A query over vertices already recentred by ``centre`` (float32 on the GPU, faces checked): MeshEvaluator's path."""
+        return cls.from_bvh(build_bvh(v32, faces), centre)
+
+    @classmethod
+    def from_bvh(cls, bvh, centre):
+        """A query over a finished tree whose vertices were recentred by ``centre``."""
         q = cls.__new__(cls)
-        q._init(v32, faces, np.asarray(centre, np.float64))
+        q._init(bvh, np.asarray(centre, np.float64))
         return q
 
-    def _init(self, v32, faces, centre):
-        self.device = v32.device
+    def _init(self, bvh, centre):
+        self.device = bvh.nodes.device
         self.centre = centre
-        self.n_faces = int(faces.shape[0])
-        self.bvh = build_bvh(v32, faces)
-        self.depth = self.bvh.depth
+        self.n_faces = int(bvh.nf)
+        self.bvh = bvh
+        self.depth = bvh.depth
 
     # ---- queries ------------------------------------------------------------------------------------------------------------------
     def _queries(self, points):
         """Recentred float32 [N, 3] on the GPU."""
-        from .metrics import _recentre
-        return _recentre(points, self.centre, self.device, 'points')
+        return recentre(points, self.centre, self.device, 'points')
 
     def _order(self, q):
         """Morton order of the queries ([N] int32, None when there is nothing to walk).  Occupancy walks them in this order: 1e6

@@ -14,26 +14,17 @@ section 3.10); components are a union-find over (face, face) pairs round every e
 (vertex, vertex) pairs ('vertex', the graph notion).  A face with an index outside [0, V) or with two equal indices is invalid: it has
 no edges, label -1, is never kept, and is counted.  Every result repeats bit for bit: the roots of the union-find are the minimum node
 index of each component whatever order the lanes ran in, the counts are integers, and the one floating-point sum (areas) is a scan in
-a fixed order.  Limits: V < 2^31, F <= 2^30.
+a fixed order.  Limits: V < 2^31, F <= 2^30.  Input: nksr_amd/mesh_input.py (float and bool faces are refused).
 """
 import numpy as np
 import torch
 
-from . import ops
+from . import mesh_input, ops
 from ._lib import (TOPO_BOUNDARY, TOPO_INTERIOR, TOPO_MAX_FACES, TOPO_MISORIENTED, TOPO_NONMANIFOLD, TOPO_TOTALS, call, lib, ptr, stream,  # noqa: F401
                    with_tmp)
+from .mesh_input import gpu_device, is64, rows3
 
 CONNECTIVITIES = ('edge', 'vertex')
-
-
-def _is64(f):
-    return int(f.dtype == torch.int64)
-
-
-def _exclusive_sum_i64(x):
-    out = torch.empty_like(x)
-    with_tmp('nksr_exclusive_sum_i64', x.device, ptr(x), ptr(out), x.numel(), stream())
-    return out
 
 
 # ---- stages (nksr_amd/tools/prof_mesh_topology.py times them one by one) --------------------------------------------------------------
@@ -44,7 +35,7 @@ def halfedge_keys(f, nv):
     ids = torch.empty(3 * nf, dtype=torch.int32, device=dev)
     valid = torch.empty(nf, dtype=torch.uint8, device=dev)
     ref = torch.empty(nv, dtype=torch.uint8, device=dev)
-    call('nksr_topo_halfedge_keys', ptr(f), _is64(f), nf, nv, ptr(keys), ptr(ids), ptr(valid), ptr(ref), stream())
+    call('nksr_topo_halfedge_keys', ptr(f), is64(f), nf, nv, ptr(keys), ptr(ids), ptr(valid), ptr(ref), stream())
     return keys, ids, valid, ref
 
 
@@ -64,7 +55,7 @@ def edge_runs(f, nv, ks, ids_sorted, ref):
     nb = int(lib.nksr_topo_run_blocks(n_half))
     counts = torch.empty(nb + 1, dtype=torch.int64, device=dev)
     call('nksr_topo_run_counts', ptr(ks), n_half, nv, ptr(counts), stream())
-    offsets = _exclusive_sum_i64(counts)
+    offsets = ops.exclusive_sum_i64(counts)
     ne = int(offsets[nb].item())
     t = EdgeTable()
     t.edges = torch.empty((ne, 2), dtype=torch.int32, device=dev)
@@ -74,7 +65,7 @@ def edge_runs(f, nv, ks, ids_sorted, ref):
     t.edge_classes = torch.empty(ne, dtype=torch.uint8, device=dev)
     t.face_adjacency = torch.empty((nf, 3), dtype=torch.int32, device=dev)
     totals = torch.empty(TOPO_TOTALS, dtype=torch.int64, device=dev)
-    call('nksr_topo_edge_classes', ptr(f), _is64(f), nf, nv, ptr(ids_sorted), ptr(t.edge_start), ne, ptr(ref), ptr(t.edge_counts),
+    call('nksr_topo_edge_classes', ptr(f), is64(f), nf, nv, ptr(ids_sorted), ptr(t.edge_start), ne, ptr(ref), ptr(t.edge_counts),
          ptr(t.edge_classes), ptr(t.face_adjacency), ptr(totals), stream())
     t.totals = [int(x) for x in totals.tolist()]
     return t
@@ -128,51 +119,16 @@ class Components:
         return keep[self.face_label.clamp(min=0).long()] & (self.face_label >= 0)
 
 
-def component_stats(c, v32, f, valid, table, ids_sorted, connectivity):
-    """Fills the per-component arrays of ``c`` (labels and n set): integer counts by atomics, boxes by ordered-integer min / max,
-    areas by a stable sort of the faces by label and a by-key scan."""
-    nf, nv, dev, n = f.shape[0], v32.shape[0], f.device, c.n
-    ne = table.edges.shape[0]
-    counts = torch.zeros((n, 4), dtype=torch.int64, device=dev)
-    c.box = torch.empty((n, 6), dtype=torch.float32, device=dev)
-    c.area = torch.zeros(n, dtype=torch.float64, device=dev)
-    if n:
-        call('nksr_topo_component_counts', ptr(c.face_label), nf, ptr(c.vertex_label), nv, ptr(ids_sorted), ptr(table.edge_start),
-             ptr(table.edge_classes), ne, n, ptr(counts), stream())
-        if connectivity == 'edge':          # vertices where components only touch: count them in every component (syncs: their number)
-            m_dev = torch.empty(1, dtype=torch.int64, device=dev)
-            call('nksr_topo_shared_corners', ptr(f), _is64(f), nf, nv, ptr(c.face_label), ptr(c.vertex_label), None, 0, ptr(m_dev), stream())
-            m = int(m_dev.item())
-            if m:
-                keys = torch.empty(m, dtype=torch.int64, device=dev)
-                call('nksr_topo_shared_corners', ptr(f), _is64(f), nf, nv, ptr(c.face_label), ptr(c.vertex_label), ptr(keys), m, ptr(m_dev), stream())
-                keys = ops.sort_keys(keys, end_bit=32 + int(n).bit_length())
-                call('nksr_topo_count_shared', ptr(keys), m, n, ptr(counts), stream())
-        call('nksr_topo_component_boxes', ptr(v32), nv, ptr(f), _is64(f), nf, ptr(c.face_label), n, ptr(c.box), stream())
-        normal = torch.empty((nf, 3), dtype=torch.float32, device=dev)
-        area = torch.empty(nf, dtype=torch.float64, device=dev)
-        call('nksr_mesh_face_areas', ptr(v32), nv, ptr(f), _is64(f), nf, ptr(normal), ptr(area), stream())
-        key = torch.where(c.face_label >= 0, c.face_label, torch.full_like(c.face_label, n)).to(torch.int64)
-        ks, order = ops.sort_pairs(key, torch.arange(nf, dtype=torch.int32, device=dev), end_bit=int(n).bit_length() + 1)
-        sums = torch.empty(nf, dtype=torch.float64, device=dev)
-        with_tmp('nksr_inclusive_sum_by_key_f64', dev, ptr(ks), ptr(area[order.long()].contiguous()), ptr(sums), nf, stream())
-        c.area = sums[torch.cumsum(counts[:, 0], 0) - 1]            # (every component has a face: the last element of its segment)
-    c.face_count, c.vertex_count, c.edge_count, c.boundary_edges = (counts[:, k].contiguous() for k in range(4))
-    c.euler = c.vertex_count - c.edge_count + c.face_count
-    c.closed = c.boundary_edges == 0
-    return c
-
-
 def compact_mesh(v, f, face_keep, colors=None):
     """(v2, f2, c2, vertex_map): the kept valid faces in their order, the vertices they name in theirs, indices rewritten (syncs)."""
     nf, nv, dev = f.shape[0], v.shape[0], f.device
     fflags = torch.empty(nf + 1, dtype=torch.int32, device=dev)
     vflags = torch.empty(nv + 1, dtype=torch.int32, device=dev)
-    call('nksr_topo_compact_mark', ptr(f), _is64(f), nf, nv, ptr(face_keep), ptr(fflags), ptr(vflags), stream())
+    call('nksr_topo_compact_mark', ptr(f), is64(f), nf, nv, ptr(face_keep), ptr(fflags), ptr(vflags), stream())
     foffs, voffs = ops.exclusive_sum_i32(fflags), ops.exclusive_sum_i32(vflags)
     f2 = torch.empty((int(foffs[nf].item()), 3), dtype=f.dtype, device=dev)
     vmap = torch.empty(nv, dtype=torch.int64, device=dev)
-    call('nksr_topo_compact_faces', ptr(f), _is64(f), nf, nv, ptr(fflags), ptr(foffs), ptr(vflags), ptr(voffs), ptr(f2), ptr(vmap), stream())
+    call('nksr_topo_compact_faces', ptr(f), is64(f), nf, nv, ptr(fflags), ptr(foffs), ptr(vflags), ptr(voffs), ptr(f2), ptr(vmap), stream())
     vkeep = vflags[:nv].bool()
     return v[vkeep], f2, None if colors is None else colors[vkeep], vmap
 
@@ -181,34 +137,37 @@ class MeshTopology:
     """Topology of one triangle mesh (v [V, 3], f [F, 3] int32 / int64) on the GPU; see the module's docstring."""
 
     def __init__(self, v, f, device=None):
-        from .metrics import _device, _rows3
-        if device is None and isinstance(v, torch.Tensor) and v.is_cuda:
-            device = v.device
-        dev = _device(device)
+        dev = gpu_device(device, like=v)
         vv = v.detach() if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
-        _rows3(vv, 'vertices')
+        rows3(vv, 'vertices')
         if not vv.dtype.is_floating_point:
             vv = vv.to(torch.float32)
-        ff = f.detach() if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(f)))
-        if ff.dtype not in (torch.int32, torch.int64):
-            if ff.dtype.is_floating_point or ff.dtype == torch.bool:
-                raise ValueError('faces: expected integer indices, got %s' % ff.dtype)
-            ff = ff.to(torch.int64)
-        if ff.numel() == 0:
-            ff = ff.reshape(0, 3)
-        _rows3(ff, 'faces')
+        ff = mesh_input.faces(f, vv.shape[0], dev, cast_float=False, check_range=False)
         if vv.shape[0] >= 1 << 31:
             raise ValueError('mesh topology: %d vertices, at most 2^31 - 1' % vv.shape[0])
         if ff.shape[0] > TOPO_MAX_FACES:
             raise ValueError('mesh topology: %d faces, at most 2^30' % ff.shape[0])
-        self.device = dev
-        self.v = vv.to(dev).contiguous()                        # the caller's precision: what compact() hands back
-        self.v32 = self.v.to(torch.float32).contiguous()        # areas and boxes
-        self.f = ff.to(dev).contiguous()
-        self.n_vertices, self.n_faces = int(self.v.shape[0]), int(self.f.shape[0])
-        keys, ids, self.face_valid, self.vertex_ref = halfedge_keys(self.f, self.n_vertices)
-        self._keys_sorted, self._ids_sorted = sort_halfedges(keys, ids, self.n_vertices)
-        self._table = edge_runs(self.f, self.n_vertices, self._keys_sorted, self._ids_sorted, self.vertex_ref)
+        self._init(vv.to(dev).contiguous(), ff)
+
+    @classmethod
+    def from_device(cls, v, f, built=None):
+        """A topology of tensors that are on the GPU already (v [V, 3] floating point, f [F, 3] int32 / int64, both contiguous)."""
+        t = cls.__new__(cls)
+        t._init(v, f, built)
+        return t
+
+    def _init(self, v, f, built=None):
+        """Runs the stages; ``built`` = (face_valid, vertex_ref, keys_sorted, ids_sorted, EdgeTable) when the caller ran them itself."""
+        self.device = v.device
+        self.v = v                                              # the caller's precision: what compact() hands back
+        self.v32 = v.to(torch.float32).contiguous()             # areas and boxes
+        self.f = f
+        self.n_vertices, self.n_faces = int(v.shape[0]), int(f.shape[0])
+        if built is None:
+            keys, ids, valid, ref = halfedge_keys(f, self.n_vertices)
+            ks, ids_sorted = sort_halfedges(keys, ids, self.n_vertices)
+            built = valid, ref, ks, ids_sorted, edge_runs(f, self.n_vertices, ks, ids_sorted, ref)
+        self.face_valid, self.vertex_ref, self._keys_sorted, self._ids_sorted, self._table = built
         (self.num_edges, self.boundary_edges, self.nonmanifold_edges, self.misoriented_edges, self.invalid_faces,
          self.referenced_vertices) = self._table.totals
         self.edges, self.edge_counts = self._table.edges, self._table.edge_counts
@@ -241,21 +200,60 @@ class MeshTopology:
         if connectivity not in CONNECTIVITIES:
             raise ValueError("connectivity must be 'edge' or 'vertex', got %r" % (connectivity,))
         if connectivity not in self._components:
-            nf, nv, dev = self.n_faces, self.n_vertices, self.device
-            c = Components()
-            if connectivity == 'edge':
-                pairs = torch.empty((3 * nf, 2), dtype=torch.int32, device=dev)
-                call('nksr_topo_face_pairs', ptr(self._keys_sorted), ptr(self._ids_sorted), 3 * nf, nv, ptr(pairs), stream())
-                c.face_label, c.n = union_find(nf, self.face_valid, pairs)
-                c.vertex_label = torch.empty(nv, dtype=torch.int32, device=dev)
-            else:
-                c.vertex_label, c.n = union_find(nv, self.vertex_ref, self.edges)
-                c.face_label = torch.empty(nf, dtype=torch.int32, device=dev)
-            call('nksr_topo_cross_labels', ptr(self.f), _is64(self.f), nf, nv, ptr(self.face_valid), int(connectivity == 'vertex'),
-                 ptr(c.face_label), ptr(c.vertex_label), stream())
-            c.connectivity = connectivity
-            self._components[connectivity] = component_stats(c, self.v32, self.f, self.face_valid, self._table, self._ids_sorted, connectivity)
+            self._components[connectivity] = self.component_stats(self.labels(connectivity))
         return self._components[connectivity]
+
+    def labels(self, connectivity):
+        """A ``Components`` with n and the labels only: hook + flatten, then the labels of the other kind of node."""
+        nf, nv, dev = self.n_faces, self.n_vertices, self.device
+        c = Components()
+        if connectivity == 'edge':
+            pairs = torch.empty((3 * nf, 2), dtype=torch.int32, device=dev)
+            call('nksr_topo_face_pairs', ptr(self._keys_sorted), ptr(self._ids_sorted), 3 * nf, nv, ptr(pairs), stream())
+            c.face_label, c.n = union_find(nf, self.face_valid, pairs)
+            c.vertex_label = torch.empty(nv, dtype=torch.int32, device=dev)
+        else:
+            c.vertex_label, c.n = union_find(nv, self.vertex_ref, self.edges)
+            c.face_label = torch.empty(nf, dtype=torch.int32, device=dev)
+        call('nksr_topo_cross_labels', ptr(self.f), is64(self.f), nf, nv, ptr(self.face_valid), int(connectivity == 'vertex'),
+             ptr(c.face_label), ptr(c.vertex_label), stream())
+        c.connectivity = connectivity
+        return c
+
+    def component_stats(self, c):
+        """Fills the per-component arrays of ``c`` (``labels``' result): integer counts by atomics, boxes by ordered-integer min / max,
+        areas by a stable sort of the faces by label and a by-key scan."""
+        v32, f, table, ids_sorted, connectivity = self.v32, self.f, self._table, self._ids_sorted, c.connectivity
+        nf, nv, dev, n = f.shape[0], v32.shape[0], f.device, c.n
+        ne = table.edges.shape[0]
+        counts = torch.zeros((n, 4), dtype=torch.int64, device=dev)
+        c.box = torch.empty((n, 6), dtype=torch.float32, device=dev)
+        c.area = torch.zeros(n, dtype=torch.float64, device=dev)
+        if n:
+            call('nksr_topo_component_counts', ptr(c.face_label), nf, ptr(c.vertex_label), nv, ptr(ids_sorted), ptr(table.edge_start),
+                 ptr(table.edge_classes), ne, n, ptr(counts), stream())
+            if connectivity == 'edge':          # vertices where components only touch: count them in every component (syncs: their number)
+                m_dev = torch.empty(1, dtype=torch.int64, device=dev)
+                call('nksr_topo_shared_corners', ptr(f), is64(f), nf, nv, ptr(c.face_label), ptr(c.vertex_label), None, 0, ptr(m_dev), stream())
+                m = int(m_dev.item())
+                if m:
+                    keys = torch.empty(m, dtype=torch.int64, device=dev)
+                    call('nksr_topo_shared_corners', ptr(f), is64(f), nf, nv, ptr(c.face_label), ptr(c.vertex_label), ptr(keys), m, ptr(m_dev), stream())
+                    keys = ops.sort_keys(keys, end_bit=32 + int(n).bit_length())
+                    call('nksr_topo_count_shared', ptr(keys), m, n, ptr(counts), stream())
+            call('nksr_topo_component_boxes', ptr(v32), nv, ptr(f), is64(f), nf, ptr(c.face_label), n, ptr(c.box), stream())
+            normal = torch.empty((nf, 3), dtype=torch.float32, device=dev)
+            area = torch.empty(nf, dtype=torch.float64, device=dev)
+            call('nksr_mesh_face_areas', ptr(v32), nv, ptr(f), is64(f), nf, ptr(normal), ptr(area), stream())
+            key = torch.where(c.face_label >= 0, c.face_label, torch.full_like(c.face_label, n)).to(torch.int64)
+            ks, order = ops.sort_pairs(key, torch.arange(nf, dtype=torch.int32, device=dev), end_bit=int(n).bit_length() + 1)
+            sums = torch.empty(nf, dtype=torch.float64, device=dev)
+            with_tmp('nksr_inclusive_sum_by_key_f64', dev, ptr(ks), ptr(area[order.long()].contiguous()), ptr(sums), nf, stream())
+            c.area = sums[torch.cumsum(counts[:, 0], 0) - 1]            # (every component has a face: the last element of its segment)
+        c.face_count, c.vertex_count, c.edge_count, c.boundary_edges = (counts[:, k].contiguous() for k in range(4))
+        c.euler = c.vertex_count - c.edge_count + c.face_count
+        c.closed = c.boundary_edges == 0
+        return c
 
     def compact(self, face_keep, colors=None):
         """(v2, f2, c2, vertex_map [V] int64: new index or -1) of the faces flagged in ``face_keep`` [F] (invalid faces are dropped):

@@ -7,7 +7,8 @@ A mesh is scored against an oriented ground-truth cloud through area-uniform sam
                 t = 0.01 ('f-score'), 0.015, 0.02 and 0.1 ('-outdoor')
 Every stage runs on the GPU (csrc/metrics.hip: face areas, the fp64 area CDF, the counter-based sampler, the fixed-order reduce;
 csrc/knn.hip: the exact nearest neighbour of every query over an octree of the other cloud).  Coordinates are recentred in float64
-by the centre of the target's bounding box before they are rounded to float32, so scenes far from the origin keep their precision.
+by the centre of the target's bounding box before they are rounded to float32, so scenes far from the origin keep their precision
+(nksr_amd/mesh_input.py, which turns every caller's array into a checked device tensor).
 Results are bitwise reproducible: the samples depend on (seed, index) only and no sum uses float atomics.
 ``o3d-iou`` (requested through ``metric_names``) is the volumetric IoU against ``onet_samples`` = (points, occupancy): the mesh's
 occupancy of the points by ray parity (``MeshQuery``, nksr_amd/mesh_query.py: a BVH over the triangles, csrc/meshquery.hip), then
@@ -16,8 +17,9 @@ sum(pd & gt) / (sum(pd | gt) + 1e-6) with integer counts, as in the reference (m
 import numpy as np
 import torch
 
-from ._lib import METRIC_FIELDS, NN_BLOCK, call, ptr, require_gpu, stream, with_tmp
+from ._lib import METRIC_FIELDS, NN_BLOCK, call, ptr, stream, with_tmp
 from .density import bbox_center
+from .mesh_input import bbox_centre, faces, gpu_device, is64, normals32, recentre
 from .mesh_query import MeshQuery, mesh_occupancy  # noqa: F401  (re-exported: nksr.metrics.MeshQuery)
 from .mesh_topology import MeshTopology  # noqa: F401  (re-exported: nksr.metrics.MeshTopology)
 from .neighbours import PointGrid, PointPyramid, choose_cell_size
@@ -28,82 +30,6 @@ _KEY_CELLS = float(1 << 18)                     # |coordinate| / cell stays belo
 IOU_RAYS = 3                                    # rays per ONet sample of 'o3d-iou' (majority of three parities)
 
 
-def _device(device):
-    if device is None:
-        device = 'cuda'
-    device = require_gpu(device)
-    if device.index is None:
-        device = torch.device('cuda', torch.cuda.current_device())
-    return device
-
-
-def _rows3(x, name):
-    shape = tuple(x.shape)
-    if len(shape) != 2 or shape[1] != 3:
-        raise ValueError('%s: expected an [N, 3] array, got shape %s' % (name, shape))
-
-
-def _bbox_centre(x):
-    """float64 centre of the bounding box of x (numpy array or tensor) as a numpy [3] array."""
-    if not isinstance(x, torch.Tensor):
-        x = np.asarray(x)
-    _rows3(x, 'target')
-    if x.shape[0] == 0:
-        raise ValueError('the target cloud is empty')
-    if isinstance(x, torch.Tensor):
-        x = x.detach()
-        lo, hi = x.amin(0).double().cpu().numpy(), x.amax(0).double().cpu().numpy()
-    else:
-        lo, hi = x.min(0).astype(np.float64), x.max(0).astype(np.float64)
-    return 0.5 * (lo + hi)
-
-
-def _recentre(x, centre, dev, name):
-    """float32 copy of x - centre on dev, the difference taken in float64."""
-    if not isinstance(x, torch.Tensor):
-        x = np.asarray(x)
-    _rows3(x, name)
-    if isinstance(x, torch.Tensor):
-        x = x.detach()
-        if x.is_cuda:
-            out = (x.to(dev, torch.float64) - torch.from_numpy(centre).to(dev)).to(torch.float32)
-        else:
-            x = x.numpy()
-    if not isinstance(x, torch.Tensor):
-        out = torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64) - centre, dtype=np.float32)).to(dev)
-    out = out.contiguous()
-    if out.numel() and not bool(torch.isfinite(out).all()):
-        raise ValueError('%s: non-finite coordinates' % name)
-    return out
-
-
-def _normals32(n, count, dev, name):
-    if n is None:
-        return None
-    _rows3(n, name)
-    t = n.detach() if isinstance(n, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(n, np.float32)))
-    t = t.to(dev, torch.float32).contiguous()
-    if t.shape[0] != count:
-        raise ValueError('%s: %d rows for %d points' % (name, t.shape[0], count))
-    if t.numel() and not bool(torch.isfinite(t).all()):
-        raise ValueError('%s: non-finite values' % name)
-    return t
-
-
-def _faces(f, nv, dev):
-    """[F, 3] int32 / int64 faces on dev (their own dtype), indices checked against nv."""
-    t = f.detach() if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(f)))
-    if t.dtype not in (torch.int32, torch.int64):
-        t = t.to(torch.int64)
-    if t.numel() == 0:
-        return t.reshape(0, 3).to(dev)
-    _rows3(t, 'faces')
-    t = t.to(dev).contiguous()
-    if int(t.min()) < 0 or int(t.max()) >= nv:
-        raise ValueError('faces: vertex index outside [0, %d)' % nv)
-    return t
-
-
 # ---- stages (nksr_amd/tools/prof_metrics.py times them one by one) -------------------------------------------------------------------
 def face_cdf(v32, f):
     """(unit face normals [F, 3] float32, inclusive float64 CDF of the face areas [F])."""
@@ -111,7 +37,7 @@ def face_cdf(v32, f):
     normal = torch.empty((nf, 3), dtype=torch.float32, device=dev)
     area = torch.empty(nf, dtype=torch.float64, device=dev)
     cdf = torch.empty(nf, dtype=torch.float64, device=dev)
-    call('nksr_mesh_face_areas', ptr(v32), v32.shape[0], ptr(f), int(f.dtype == torch.int64), nf, ptr(normal), ptr(area), stream())
+    call('nksr_mesh_face_areas', ptr(v32), v32.shape[0], ptr(f), is64(f), nf, ptr(normal), ptr(area), stream())
     if nf:
         with_tmp('nksr_inclusive_sum_f64', dev, ptr(area), ptr(cdf), nf, stream())
     return normal, cdf
@@ -123,7 +49,7 @@ def sample_from_cdf(v32, f, fnormal, cdf, n, seed):
     xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
     nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
     face = torch.empty(n, dtype=torch.int64, device=dev)
-    call('nksr_mesh_sample', ptr(v32), v32.shape[0], ptr(f), int(f.dtype == torch.int64), f.shape[0], ptr(cdf), ptr(fnormal), n,
+    call('nksr_mesh_sample', ptr(v32), v32.shape[0], ptr(f), is64(f), f.shape[0], ptr(cdf), ptr(fnormal), n,
          int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(xyz), ptr(nrm), ptr(face), stream())
     return xyz, nrm, face
 
@@ -184,12 +110,12 @@ def sample_surface(v, f, n, seed=0, device=None):
     """n area-uniform samples of the mesh (v [V, 3], f [F, 3] int32 / int64) on the GPU, in float32 coordinates as given:
     (points [n, 3], unit normals of their triangles [n, 3], face index [n] int64).  Sample i depends on (seed, i) only
     (Philox4x32-10, include/nksr_hip.h ``nksr_mesh_sample``); triangles of zero area are never picked."""
-    dev = _device(device if device is not None else (v.device if isinstance(v, torch.Tensor) and v.is_cuda else None))
+    dev = gpu_device(device, like=v)
     n = int(n)
     if n < 0:
         raise ValueError('sample_surface: n must be >= 0')
-    v32 = _recentre(v, np.zeros(3), dev, 'vertices')
-    ff = _faces(f, v32.shape[0], dev)
+    v32 = recentre(v, np.zeros(3), dev, 'vertices')
+    ff = faces(f, v32.shape[0], dev, cast_float=True, check_range=True)
     fn, cdf = face_cdf(v32, ff)
     if n and (ff.shape[0] == 0 or not float(cdf[-1]) > 0.0):
         raise ValueError('sample_surface: the mesh has no area')
@@ -199,12 +125,12 @@ def sample_surface(v, f, n, seed=0, device=None):
 def distance_p2p(src, nsrc, tgt, ntgt, device=None):
     """Nearest-neighbour distance of every src point to tgt and |unit n_src . unit n_nn| (a zero normal gives 0) as [N] float32
     tensors on the GPU; dot is None unless both normal sets are given.  Exact: every query gets its nearest target point."""
-    dev = _device(device)
-    centre = _bbox_centre(tgt)
-    t = _recentre(tgt, centre, dev, 'tgt')
-    q = _recentre(src, centre, dev, 'src')
-    cloud = Cloud(t, _normals32(ntgt, t.shape[0], dev, 'ntgt'))
-    qn = _normals32(nsrc, q.shape[0], dev, 'nsrc')
+    dev = gpu_device(device)
+    centre = bbox_centre(tgt)
+    t = recentre(tgt, centre, dev, 'tgt')
+    q = recentre(src, centre, dev, 'src')
+    cloud = Cloud(t, normals32(ntgt, t.shape[0], dev, 'ntgt'))
+    qn = normals32(nsrc, q.shape[0], dev, 'nsrc')
     dist = torch.empty(q.shape[0], dtype=torch.float32, device=dev)
     dot = torch.empty(q.shape[0], dtype=torch.float32, device=dev) if (qn is not None and cloud.normal is not None) else None
     cloud.nearest(q, qn, dist=dist, dot=dot, sums=False)
@@ -221,7 +147,7 @@ class MeshEvaluator:
     def __init__(self, n_points=100000, metric_names=ALL_METRICS, device=None):
         self.n_points = int(n_points)
         self.metric_names = list(metric_names)
-        self.device = _device(device)
+        self.device = gpu_device(device)
 
     def _filter(self, d):
         return {k: d[k] for k in self.metric_names if k in d}
@@ -241,17 +167,17 @@ class MeshEvaluator:
         if want_iou and onet_samples is None:
             raise ValueError("'o3d-iou' needs onet_samples = (points, occupancy)")
         dev = self.device
-        centre = _bbox_centre(pointcloud_tgt)
-        v32 = _recentre(mesh.v, centre, dev, 'mesh.v')
-        ff = _faces(mesh.f, v32.shape[0], dev)
+        centre = bbox_centre(pointcloud_tgt)
+        v32 = recentre(mesh.v, centre, dev, 'mesh.v')
+        ff = faces(mesh.f, v32.shape[0], dev, cast_float=True, check_range=True)
         if ff.shape[0] == 0 or self.n_points == 0:
             return self._nan()
         fn, cdf = face_cdf(v32, ff)
         if not float(cdf[-1]) > 0.0:
             return self._nan()
         p, n, _ = sample_from_cdf(v32, ff, fn, cdf, self.n_points, seed)
-        t = _recentre(pointcloud_tgt, centre, dev, 'pointcloud_tgt')
-        out = self._evaluate(p, n, t, _normals32(normals_tgt, t.shape[0], dev, 'normals_tgt'))
+        t = recentre(pointcloud_tgt, centre, dev, 'pointcloud_tgt')
+        out = self._evaluate(p, n, t, normals32(normals_tgt, t.shape[0], dev, 'normals_tgt'))
         if want_iou:
             out['o3d-iou'] = self._iou(MeshQuery.recentred(v32, ff, centre), onet_samples)
         return out
@@ -272,10 +198,10 @@ class MeshEvaluator:
     def evaluate(self, pointcloud, pointcloud_tgt, normals=None, normals_tgt=None):
         """The metric dict of a given sample set against the target (the reference's ``_evaluate``)."""
         dev = self.device
-        centre = _bbox_centre(pointcloud_tgt)
-        p = _recentre(pointcloud, centre, dev, 'pointcloud')
-        t = _recentre(pointcloud_tgt, centre, dev, 'pointcloud_tgt')
-        return self._evaluate(p, _normals32(normals, p.shape[0], dev, 'normals'), t, _normals32(normals_tgt, t.shape[0], dev, 'normals_tgt'))
+        centre = bbox_centre(pointcloud_tgt)
+        p = recentre(pointcloud, centre, dev, 'pointcloud')
+        t = recentre(pointcloud_tgt, centre, dev, 'pointcloud_tgt')
+        return self._evaluate(p, normals32(normals, p.shape[0], dev, 'normals'), t, normals32(normals_tgt, t.shape[0], dev, 'normals_tgt'))
 
     def _evaluate(self, p, pn, t, tn):
         if p.shape[0] == 0:

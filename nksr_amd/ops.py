@@ -140,6 +140,13 @@ def exclusive_sum_i32(x):
     return out
 
 
+def exclusive_sum_i64(x):
+    out = torch.empty_like(x)
+    if x.numel():
+        with_tmp('nksr_exclusive_sum_i64', x.device, ptr(x), ptr(out), x.numel(), stream())
+    return out
+
+
 def compact(flags):
     """Ordered indices (int32) of the non-zero int32 flags (syncs to read the count)."""
     n = flags.numel()

@@ -16,7 +16,7 @@ import json
 import numpy as np
 import torch
 
-from nksr_amd import mesh_query, metrics
+from nksr_amd import mesh_input, mesh_query
 
 
 def _events(n):
@@ -39,8 +39,7 @@ def stages(v32, f, q32):
     mq.refit(bvh, v32, f, order, parent)
     mq.finish(bvh)
     ev[4].record()
-    q = mq.MeshQuery.__new__(mq.MeshQuery)
-    q.device, q.centre, q.n_faces, q.bvh, q.depth = v32.device, np.zeros(3), f.shape[0], bvh, bvh.depth
+    q = mq.MeshQuery.from_bvh(bvh, np.zeros(3))
     qc, qi = mq.morton(q32, box)
     qorder = mq.sort_codes(qc, qi)[1]
     ev[5].record()
@@ -98,10 +97,10 @@ def main():
     for name, make in (('configs1', case_configs1), ('scene_1m', case_scene_1m)):
         mesh, n = make(dev)
         vn = mesh.v.cpu().numpy()
-        centre = metrics._bbox_centre(vn)
-        v32 = metrics._recentre(vn, centre, dev, 'v')
-        f = metrics._faces(mesh.f, v32.shape[0], dev)
-        q32 = metrics._recentre(onet_queries(vn, n), centre, dev, 'q')
+        centre = mesh_input.bbox_centre(vn)
+        v32 = mesh_input.recentre(vn, centre, dev, 'v')
+        f = mesh_input.faces(mesh.f, v32.shape[0], dev, cast_float=True, check_range=True)
+        q32 = mesh_input.recentre(onet_queries(vn, n), centre, dev, 'q')
         stages(v32, f, q32)                                             # warm-up
         runs = []
         for _ in range(args.reps):

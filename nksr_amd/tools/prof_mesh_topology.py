@@ -20,42 +20,23 @@ import torch
 from nksr_amd import mesh_topology as mt
 
 
-def _components(t, connectivity):
-    """The labels of MeshTopology.components without the statistics."""
-    nf, nv, dev = t.n_faces, t.n_vertices, t.device
-    c = mt.Components()
-    if connectivity == 'edge':
-        pairs = torch.empty((3 * nf, 2), dtype=torch.int32, device=dev)
-        mt.call('nksr_topo_face_pairs', mt.ptr(t._keys_sorted), mt.ptr(t._ids_sorted), 3 * nf, nv, mt.ptr(pairs), mt.stream())
-        c.face_label, c.n = mt.union_find(nf, t.face_valid, pairs)
-        c.vertex_label = torch.empty(nv, dtype=torch.int32, device=dev)
-    else:
-        c.vertex_label, c.n = mt.union_find(nv, t.vertex_ref, t.edges)
-        c.face_label = torch.empty(nf, dtype=torch.int32, device=dev)
-    mt.call('nksr_topo_cross_labels', mt.ptr(t.f), mt._is64(t.f), nf, nv, mt.ptr(t.face_valid), int(connectivity == 'vertex'),
-            mt.ptr(c.face_label), mt.ptr(c.vertex_label), mt.stream())
-    return c
-
-
 def stages(v, f):
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(9)]
-    t = mt.MeshTopology.__new__(mt.MeshTopology)
-    t.device, t.v, t.v32, t.f, t.n_vertices, t.n_faces = v.device, v, v, f, v.shape[0], f.shape[0]
+    nv = v.shape[0]
     ev[0].record()
-    keys, ids, t.face_valid, t.vertex_ref = mt.halfedge_keys(f, t.n_vertices)
+    keys, ids, valid, ref = mt.halfedge_keys(f, nv)
     ev[1].record()
-    t._keys_sorted, t._ids_sorted = mt.sort_halfedges(keys, ids, t.n_vertices)
+    ks, ids_sorted = mt.sort_halfedges(keys, ids, nv)
     ev[2].record()
-    t._table = mt.edge_runs(f, t.n_vertices, t._keys_sorted, t._ids_sorted, t.vertex_ref)
-    t.edges = t._table.edges
+    t = mt.MeshTopology.from_device(v, f, (valid, ref, ks, ids_sorted, mt.edge_runs(f, nv, ks, ids_sorted, ref)))
     ev[3].record()
-    ce = _components(t, 'edge')
+    ce = t.labels('edge')
     ev[4].record()
-    cv = _components(t, 'vertex')
+    cv = t.labels('vertex')
     ev[5].record()
-    mt.component_stats(ce, t.v32, f, t.face_valid, t._table, t._ids_sorted, 'edge')
+    t.component_stats(ce)
     ev[6].record()
-    mt.component_stats(cv, t.v32, f, t.face_valid, t._table, t._ids_sorted, 'vertex')
+    t.component_stats(cv)
     ev[7].record()
     keep = ce.face_mask(ce.select(min_area_ratio=0.01)).to(torch.uint8)
     v2, f2, _, _ = mt.compact_mesh(v, f, keep)
@@ -63,7 +44,7 @@ def stages(v, f):
     torch.cuda.synchronize()
     names = ['keys', 'sort', 'runs', 'components_edge', 'components_vertex', 'stats_edge', 'stats_vertex', 'compaction']
     out = {k: ev[i].elapsed_time(ev[i + 1]) for i, k in enumerate(names)}
-    info = {'edges': t._table.totals[0], 'boundary_edges': t._table.totals[1], 'nonmanifold_edges': t._table.totals[2],
+    info = {'edges': t.num_edges, 'boundary_edges': t.boundary_edges, 'nonmanifold_edges': t.nonmanifold_edges,
             'components_edge': ce.n, 'components_vertex': cv.n, 'faces_kept': int(f2.shape[0])}
     return out, info
 

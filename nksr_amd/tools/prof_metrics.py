@@ -16,7 +16,7 @@ import time
 import numpy as np
 import torch
 
-from nksr_amd import metrics
+from nksr_amd import mesh_input, metrics
 
 
 def _events(n):
@@ -24,11 +24,11 @@ def _events(n):
 
 
 def gpu_stages(mesh, gt, gtn, n, dev):
-    centre = metrics._bbox_centre(gt)
-    v32 = metrics._recentre(mesh.v, centre, dev, 'v')
-    f = metrics._faces(mesh.f, v32.shape[0], dev)
-    t = metrics._recentre(gt, centre, dev, 'gt')
-    tn = metrics._normals32(gtn, t.shape[0], dev, 'gtn')
+    centre = mesh_input.bbox_centre(gt)
+    v32 = mesh_input.recentre(mesh.v, centre, dev, 'v')
+    f = mesh_input.faces(mesh.f, v32.shape[0], dev, cast_float=True, check_range=True)
+    t = mesh_input.recentre(gt, centre, dev, 'gt')
+    tn = mesh_input.normals32(gtn, t.shape[0], dev, 'gtn')
     ev = _events(8)
     ev[0].record()
     fn, cdf = metrics.face_cdf(v32, f)

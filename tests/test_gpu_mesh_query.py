@@ -180,6 +180,50 @@ def test_occupancy_invariances(recipe_meshes):
     pu.report('mesh_query:invariances', faces=len(f), queries=len(p), depth=a.depth, away=int(away.sum()))
 
 
+def test_one_mesh_in_every_input_form():
+    """The unit cube far from the origin (every coordinate exact in float32) as numpy arrays, CPU tensors and GPU tensors, with int32
+    and int64 faces: MeshQuery, MeshTopology and sample_surface answer bit for bit alike.  Faces stored as floating point are read
+    by MeshQuery and sample_surface and refused by MeshTopology (the two readers of nksr_amd/mesh_input.py)."""
+    from nksr_amd.mesh_query import MeshQuery
+    from nksr_amd.mesh_topology import MeshTopology
+    from nksr_amd.metrics import sample_surface
+    dev = _dev()
+    off = np.array([1048576.0, -2097152.0, 4194304.0])
+    v = np.array([[i & 1, i >> 1 & 1, i >> 2] for i in range(8)], np.float64) + off
+    f = np.array([[0, 2, 3], [0, 3, 1], [4, 5, 7], [4, 7, 6], [0, 1, 5], [0, 5, 4], [2, 7, 3], [2, 6, 7], [0, 4, 6], [0, 6, 2], [1, 3, 7], [1, 7, 5]],
+                 np.int64)
+    assert np.array_equal(v.astype(np.float32).astype(np.float64), v)
+    c = v - off
+    assert np.einsum('ij,ij->', c[f[:, 0]], np.cross(c[f[:, 1]], c[f[:, 2]])) / 6.0 == 1.0        # outward: the signed volume
+    u = np.random.RandomState(7).uniform(-0.5, 1.5, (64, 3))
+    q = u + off                                                                     # float64 in every form: float32 has no such points
+    inside = np.all((u > 0) & (u < 1), axis=1)
+    assert 2 < inside.sum() < 62
+    forms = {'numpy_f64_i64': (v, f, q),
+             'cpu_f32_i32': (torch.from_numpy(v.astype(np.float32)), torch.from_numpy(f.astype(np.int32)), torch.from_numpy(q)),
+             'gpu_f32_i64': (torch.from_numpy(v.astype(np.float32)).to(dev), torch.from_numpy(f).to(dev), torch.from_numpy(q).to(dev))}
+    forms['float_faces'] = (v, f.astype(np.float64), q)
+
+    def answers(vv, ff, qq):
+        mq = MeshQuery(vv, ff)
+        d, face = mq.distance(qq)
+        return (d, face, mq.occupancy(qq, rays=3), mq.signed_distance(qq)) + sample_surface(vv, ff, n=256, seed=7)
+    names = ('distance', 'face', 'occupancy', 'signed_distance', 'sample points', 'sample normals', 'sample faces')
+    base = answers(*forms['numpy_f64_i64'])
+    assert np.array_equal(base[2].cpu().numpy(), inside)
+    assert base[4].dtype == torch.float32 and base[6].dtype == torch.int64 and int(base[6].min()) >= 0 and int(base[6].max()) < 12
+    for form, args in forms.items():
+        for name, a, b in zip(names, answers(*args), base):
+            assert a.is_cuda and a.dtype == b.dtype and a.shape == b.shape, (form, name)
+            assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), (form, name)
+    for form in ('numpy_f64_i64', 'cpu_f32_i32', 'gpu_f32_i64'):
+        t = MeshTopology(*forms[form][:2])
+        totals = (t.num_edges, t.boundary_edges, t.nonmanifold_edges, t.misoriented_edges, t.invalid_faces, t.referenced_vertices)
+        assert totals == (18, 0, 0, 0, 0, 8) and t.euler_characteristic == 2, (form, totals)
+    with pytest.raises(ValueError, match='expected integer indices'):
+        MeshTopology(v, f.astype(np.float64))
+
+
 # ---- 4. distance -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('kind', ['sphere', 'torus', 'rbox'])
 def test_distance_against_the_fp64_brute_force(kind, recipe_meshes):
@@ -256,7 +300,7 @@ def test_a_tree_deeper_than_the_stack_is_refused(monkeypatch):
 
 # ---- 5. o3d-iou -------------------------------------------------------------------------------------------------------------------
 def test_eval_mesh_iou_is_the_formula_on_mesh_query(recipe_meshes):
-    from nksr_amd import metrics
+    from nksr_amd import mesh_input, metrics
     from nksr_amd.fields.base_field import MeshingResult
     from nksr.metrics import MeshEvaluator
     from conftest import make_cloud
@@ -267,9 +311,10 @@ def test_eval_mesh_iou_is_the_formula_on_mesh_query(recipe_meshes):
     m = ev.eval_mesh(mesh, gt, gtn, onet_samples=[p, occ])
     assert sorted(m) == ['chamfer-L1', 'o3d-iou']
     # the same frame as eval_mesh: everything recentred by the target's box centre
-    c = metrics._bbox_centre(gt)
-    v32 = metrics._recentre(mesh.v, c, _dev(), 'v')
-    pd = metrics.MeshQuery.recentred(v32, metrics._faces(mesh.f, v32.shape[0], _dev()), c).occupancy(p, rays=3).cpu().numpy()
+    c = mesh_input.bbox_centre(gt)
+    v32 = mesh_input.recentre(mesh.v, c, _dev(), 'v')
+    ff = mesh_input.faces(mesh.f, v32.shape[0], _dev(), cast_float=True, check_range=True)
+    pd = metrics.MeshQuery.recentred(v32, ff, c).occupancy(p, rays=3).cpu().numpy()
     ref = np.sum(pd & occ) / (np.sum(pd | occ) + 1e-6)
     assert m['o3d-iou'] == ref
     self_iou = ev.eval_mesh(mesh, gt, gtn, onet_samples=(torch.from_numpy(p), torch.from_numpy(pd.astype(np.float32))))['o3d-iou']
