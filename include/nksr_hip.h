@@ -777,6 +777,56 @@ int nksr_topo_compact_mark(const void* faces, int faces_int64, int64_t nf, int64
 int nksr_topo_compact_faces(const void* faces, int faces_int64, int64_t nf, int64_t nv, const int32_t* face_flags, const int32_t* face_offsets,
                             const int32_t* vertex_flags, const int32_t* vertex_offsets, void* faces_out, int64_t* vertex_map_out, void* stream);
 
+/* ---- normal orientation without sensors (csrc/orient.hip; nksr_amd/orient.py orient_graph) -------------
+ * Hoppe et al. 1992: the minimum spanning forest of the k-nearest-neighbour graph under the weight 1 - |n_i . n_j|, sign flips
+ * propagated along it.  DEFINITION (restated in tests/orient_ref.py; every output is a function of the input alone):
+ *   input    xyz [n, 3], normal [n, 3] fp32 (finite, any sign, |component| < 2^60), idx [n, k] int32, 1 <= k <= 32, n < 2^31,
+ *            n k < 2^32.  An entry of idx that is < 0, >= n or equal to its row index is ignored; duplicates are allowed.  The directed
+ *            slot s = i k + c stands for the undirected edge {i, idx[i, c]}.
+ *   dot      dot(a, b) = fl32(fl32(fl32(a0 b0) + fl32(a1 b1)) + fl32(a2 b2)): round-to-nearest products and sums, never fused
+ *            (symmetric in a, b; np.float32 arithmetic gives the same bits).
+ *   weight   w = max(fl32(1 - |dot(n_i, n_j)|), 0);  flip bit of the edge = dot(n_i, n_j) < 0.
+ *   key      (bits(w) << 32) | s, 64 bits: w >= 0, so its bit pattern orders as an unsigned integer, and no two slots share a key: the
+ *            minimum spanning forest of the multigraph of all slots -- a slot counts for the components of BOTH its end points, so the
+ *            graph is the symmetrised one although idx is not symmetric -- is unique.
+ *   relative sign of a point = XOR of the edge flip bits along the forest path to a fixed point of its component.
+ *   global sign of a component, mode 0 ('+z'): its point of largest z (-0 counts as +0; the lowest index on a tie) ends with n_z >= 0;
+ *            mode 1 (viewpoint v): with t = fl32(v - x) per axis, its point of smallest dot(t, t) (the lowest index on a tie) ends with
+ *            dot(n, t) >= 0.
+ *   outputs  flipped [n] uint8, normal_out = flipped ? -normal : normal, and the component of every point.
+ * One Boruvka round (the host loops until one component is left or a round hooks nothing; Python: orient._forest):
+ *   propose  every slot of a point that is not `done` and whose end points lie in different components takes the 64-bit minimum of
+ *            its key into best[] of both components' representatives (rep [n]; best [n] starts as all ones).  The lanes of a wavefront
+ *            that share a representative reduce their keys first.  A point whose neighbours all share its component is marked done
+ *            for good.  order [n] (may be NULL) = the point every thread takes (a Morton order keeps a wavefront inside one component).
+ *            counters[1] += points still active.
+ *   hook     every representative r with a finite best[r] links to the representative on the other side of that slot, with the parity
+ *            par[u] ^ par[v] ^ flip(u, v); two representatives that chose the same slot: the lower one stays a root.  link / lpar [n]
+ *            are written for representatives only (a root links to itself, parity 0).  counters[0] += links made.
+ *   jump     one pointer-doubling step over the representatives: link_out[r] = link_in[link_in[r]], parities XORed; ping-pong buffers,
+ *            ceil(log2(links made)) steps flatten every chain.
+ *   relabel  rep[i] = link[rep[i]], par[i] ^= lpar[rep[i]], best[i] = all ones.
+ * After the loop: seeds (seed_key [n] zeroed, min_index [n] filled with 0x7FFFFFFF beforehand): per representative the 64-bit maximum of
+ * (ordered key << 32) | ~index over its points and the minimum point index; apply: the outputs, parent_out[i] = the minimum index of
+ * i's component and root_flags_out [n + 1] = (parent_out[i] == i), then a 0 -- the inputs of nksr_exclusive_sum_i32 / nksr_uf_labels,
+ * so dense ids ascend with the components' minimum point index. */
+#define NKSR_ORIENT_MAX_K 32
+#define NKSR_ORIENT_SEED_Z 0
+#define NKSR_ORIENT_SEED_VIEWPOINT 1
+int nksr_orient_init(int64_t n, int32_t* rep, uint8_t* par, uint8_t* done, uint64_t* best, void* stream);
+int nksr_orient_propose(const float* normal, const int32_t* idx, int64_t n, int k, const int32_t* order, const int32_t* rep, uint8_t* done,
+                        uint64_t* best, int32_t* counters, void* stream);
+int nksr_orient_hook(const float* normal, const int32_t* idx, int64_t n, int k, const int32_t* rep, const uint8_t* par, const uint64_t* best,
+                     int32_t* link_out, uint8_t* lpar_out, int32_t* counters, void* stream);
+int nksr_orient_jump(const int32_t* rep, int64_t n, const int32_t* link_in, const uint8_t* lpar_in, int32_t* link_out, uint8_t* lpar_out,
+                     void* stream);
+int nksr_orient_relabel(int64_t n, int32_t* rep, uint8_t* par, const int32_t* link, const uint8_t* lpar, uint64_t* best, void* stream);
+int nksr_orient_seeds(const float* xyz, int64_t n, const int32_t* rep, int mode, float vx, float vy, float vz, uint64_t* seed_key,
+                      int32_t* min_index, void* stream);
+int nksr_orient_apply(const float* xyz, const float* normal, int64_t n, const int32_t* rep, const uint8_t* par, const uint64_t* seed_key,
+                      const int32_t* min_index, int mode, float vx, float vy, float vz, uint8_t* flipped_out, float* normal_out,
+                      int32_t* parent_out, int32_t* root_flags_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

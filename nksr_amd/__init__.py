@@ -9,12 +9,12 @@ use: ``Reconstructor``, ``NKSRNetwork``, ``SparseFeatureH
 from . import cloud, configs, fields, metrics, svh, utils
 from .mesh_topology import MeshTopology
 from .nn.network import NKSRNetwork
-from .preprocess import (compose_preprocess_fns, get_estimate_normal_preprocess_fn, get_radius_outlier_preprocess_fn,
-                         get_statistical_outlier_preprocess_fn, get_voxel_downsample_preprocess_fn)
+from .preprocess import (compose_preprocess_fns, get_estimate_normal_preprocess_fn, get_estimate_oriented_normal_preprocess_fn,
+                         get_radius_outlier_preprocess_fn, get_statistical_outlier_preprocess_fn, get_voxel_downsample_preprocess_fn)
 from .reconstructor import Reconstructor
 from .svh import SparseFeatureHierarchy
 
 __all__ = ['Reconstructor', 'NKSRNetwork', 'SparseFeatureHierarchy', 'get_estimate_normal_preprocess_fn', 'MeshTopology',
            'get_voxel_downsample_preprocess_fn', 'get_radius_outlier_preprocess_fn', 'get_statistical_outlier_preprocess_fn',
-           'compose_preprocess_fns', 'fields', 'svh', 'configs', 'utils', 'metrics', 'cloud']
+           'get_estimate_oriented_normal_preprocess_fn', 'compose_preprocess_fns', 'fields', 'svh', 'configs', 'utils', 'metrics', 'cloud']
 __version__ = '0.1.0'

@@ -9,6 +9,8 @@ the neighbour search the package already runs for its normals, its SDF ground tr
   * ``voxel_downsample``: one point per occupied voxel, the mean (or the input point nearest the mean) of every attribute
     (csrc/cloud.hip ``k_voxel_reduce``: fp64 sums in a fixed order, no atomics, bitwise repeatable).
   * ``radius_outlier_mask`` / ``statistical_outlier_mask``.
+  * ``orient_graph`` / ``orient_normals`` / ``estimate_normals`` (nksr_amd/orient.py, csrc/orient.hip): oriented normals for a cloud
+    that has positions only -- signs propagated along the minimum spanning forest of the kNN graph.
 ``nksr_amd.preprocess`` wraps them as ``preprocess_fn`` for ``Reconstructor.reconstruct``.  GPU tensors only.
 """
 import torch
@@ -16,6 +18,7 @@ import torch
 from . import ops
 from ._lib import call, ptr, require_gpu, stream
 from .neighbours import MAX_K, _RINGS, PointGrid, PointPyramid, _grid_args, choose_cell_size, search_every_scale
+from .orient import OrientedNormals, estimate_normals, orient_graph, orient_normals  # noqa: F401  (part of this module's surface)
 from .svh import inv_w0_f32
 
 
@@ -127,6 +130,12 @@ class CloudIndex:
         """float32 [N]: mean distance of every point to its k nearest OTHER points (the mean is taken in fp64 and rounded once)."""
         _, dist = self.knn(k, exclude_self=True)
         return dist.double().mean(dim=1).float()
+
+    def orient_normals(self, normal, k=16, seed='+z', viewpoint=None):
+        """``orient.orient_normals`` on this index: ``normal`` [N, 3] (any sign) oriented along the minimum spanning forest of
+        ``knn(k, exclude_self=True)`` -> ``OrientedNormals``.  The kernels visit the points in the grid's Morton order."""
+        from .orient import _orient_on_index
+        return _orient_on_index(self, normal, k, seed, viewpoint)
 
     # ---- fixed-radius neighbour count ----------------------------------------------------------------------------------------
     def _radius_grid(self, radius):

@@ -17,6 +17,21 @@ def get_estimate_normal_preprocess_fn(knn=64, deg=85.0):
     return fn
 
 
+def get_estimate_oriented_normal_preprocess_fn(knn=64, orient_k=16, seed='+z', viewpoint=None):
+    """For a cloud that has positions only: ``(xyz, None, sensor-or-None) -> (xyz', normal', None)`` by ``cloud.estimate_normals`` --
+    kNN-PCA normals, oriented along the minimum spanning forest of the ``orient_k``-nearest-neighbour graph, every connected component
+    signed by ``seed`` / ``viewpoint``; a sensor that is given is not used.  Orientation is a property of the WHOLE cloud: under
+    ``reconstruct(..., chunk_size > 0)`` this function would run per chunk, and the open piece inside a chunk cannot be signed by the
+    '+z' rule -- call ``cloud.estimate_normals`` on the whole cloud first and pass ``normal=``."""
+    def fn(xyz, normal, sensor):
+        from .orient import estimate_normals
+        if normal is not None:
+            raise RuntimeError('normal already exists')
+        xyz, normal = estimate_normals(xyz, knn=knn, orient_k=orient_k, seed=seed, viewpoint=viewpoint)
+        return xyz, normal, None
+    return fn
+
+
 def get_voxel_downsample_preprocess_fn(voxel_size, reduce='mean'):
     """One point per voxel of size ``voxel_size`` (``cloud.voxel_downsample``; colours do not fit the three slots: call it directly)."""
     def fn(xyz, normal, sensor):
