@@ -2,7 +2,7 @@
 ``solve_non_fused`` runs under autograd at models/nksr_net.py:105-112 and the loss back-propagates into the basis features
 and the interpolator weights).  The solve-time path never comes here: rows, operator, PCG and evaluation are HIP
 (csrc/kfield.hip, fused.hip, pcg.hip).  What this file is for: the vector-Jacobian products  sum_r g_r . dR_r/dtheta  that the
-implicit-function backward of the solve and of evaluate_f need (kernel_field._SolveFunction / _EvaluateFunction).  They are
+implicit-function backward of the solve and of evaluate_f need (autograd._SolveFunction / _EvaluateFunction).  They are
 taken by torch autograd through this statement of  R(theta)  (DESIGN.md section 2.3):
 
     K_d(x, c_j) = <phi_d(x), psi_j> B((x - c_j) / w_d),   phi_d(x) = t + MLP_d(t),  t = trilinear interpolation of the level's

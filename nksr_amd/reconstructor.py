@@ -36,9 +36,9 @@ class Reconstructor:
         self.chunk_spill_dir = None      # chunk mode, batches parked on a CPU chunk_tmp_device: a directory -> the parked batches live in unlinked files there
         #                                  (chunking.spill_to_disk: out-of-core beyond host memory; not part of the reference surface)
         self.coarse_precond = None  # matrix-free solve: None = automatic (coarse-level block preconditioner for 5+ levels), False = Jacobi only,
-        #                             or {'first_level', 'steps', 'ratio'} (fields/kernel_field.py _coarse_precond)
+        #                             or {'first_level', 'steps', 'ratio'} (fields/coarse_precond.py coarse_precond)
         self.row_format = None      # matrix-free solve: None / 'dense' = 27-slot kernel rows (the fast one), 'factors' = 16-byte factor records the sweep
-        #                             rebuilds the rows from (kernel_dim 4: a fifth of the row memory, twice the time per application; fields/kernel_field.py)
+        #                             rebuilds the rows from (kernel_dim 4: a fifth of the row memory, twice the time per application; fields/kernel_field.py _row_format, fields/operator_setup.py)
         self.keep_solve_inputs = False   # parity tests: the field keeps the site sets / weights of its solve (field._solve_inputs)
         self.col_format = 1        # physical layout of the assembled matrix (include/nksr_hip.h); int32 columns when M > 2^21
 

@@ -31,7 +31,7 @@ def spmv(rowptr, cols, vals, x):
 
 def pcg_solve(rowptr, cols, vals, diag, b, tol=1e-5, max_iter=2000, check_every=16, workspace=None, precond=None):
     """Returns (x, iterations, relative residual).  x0 = 0, stop on ||r|| <= tol ||b||.  ``precond``: a CoarsePrecondT
-    (KernelField._coarse_precond) -- Chebyshev steps on the coarse levels' diagonal block instead of Jacobi there; if that
+    (fields/coarse_precond.py: coarse_precond) -- Chebyshev steps on the coarse levels' diagonal block instead of Jacobi there; if that
     polynomial loses definiteness (r.z <= 0) the solve restarts with Jacobi alone on the device (``last_fallbacks`` counts it)."""
     global last_fallbacks
     M = b.numel()

@@ -1,5 +1,5 @@
 """ONE field, no chunk_size, through the matrix-free solve (the assembled system of such a cloud has nnz >= 2^31 and is refused:
-fields/kernel_field.py assemble).  Reference call: examples/recons_waymo.py:30-37 (whole sequence in one reconstruct()).
+fields/assembly.py assemble).  Reference call: examples/recons_waymo.py:30-37 (whole sequence in one reconstruct()).
 python -m nksr_amd.tools.stress_single_field [points=8000000] [reps=2]"""
 import sys
 import time

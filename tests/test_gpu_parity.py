@@ -255,8 +255,9 @@ def test_fused_operator_matches_the_assembled_matrix(approx, row_format, monkeyp
 
 def test_row_order_by_rank_passes_equals_the_sorted_merge(monkeypatch):
     """The shared Morton-ordered row list of the two site sets: first rows from two rank passes over the already sorted key lists
-    (nksr_rank_sorted) against the radix sort of the concatenated keys + scan + scatter -- rows, row cells and targets bit for bit;
-    the primitive itself against torch.searchsorted, both bounds, with runs of equal keys."""
+    (nksr_rank_sorted) against the radix sort of the concatenated keys + scan + scatter -- rows, row cells and targets bit for bit,
+    for both sets and either set alone, without segments and with two (then also item_seg and pad_rows); the primitive itself
+    against torch.searchsorted, both bounds, with runs of equal keys."""
     from nksr_amd.fields import KernelField
     from nksr_amd._lib import call, ptr, stream
     rs = np.random.RandomState(3)
@@ -271,19 +272,33 @@ def test_row_order_by_rank_passes_equals_the_sorted_merge(monkeypatch):
     t = lambda x: torch.from_numpy(x).to(_dev())
     nxyz = np.concatenate([oh.levels[0].centers(), oh.levels[1].centers()])
     nval = np.random.RandomState(5).randn(len(nxyz), 3).astype(np.float32)
-    out = {}
-    for mode in ('merge', 'sort'):
-        monkeypatch.setenv('NKSR_ROW_ORDER', mode)
-        op = fld.fused_operator(t(xyz), t(nxyz), t(nval), 1e4 / len(xyz), 1e2 / len(nxyz))
-        if op['row_format'] == 'factors':
-            n = op['op'].depth * op['rows_total'] * 4
-            rows = torch.cat([op['fac_vec'][:n], op['fac_pos'][:op['rows_total'] * 4]])
-        else:
-            rows = fld.dense_rows(op).reshape(-1)
-        out[mode] = (rows.clone(), op['row_cells'].clone(), op['targets_all'].clone(), op['rows_total'])
-    assert out['merge'][3] == out['sort'][3]
-    assert torch.equal(out['merge'][1], out['sort'][1]) and torch.equal(out['merge'][2], out['sort'][2])
-    assert torch.equal(out['merge'][0].view(torch.int32), out['sort'][0].view(torch.int32))
+    # with two segments cut from the sorted coarsest-level keys (only fused_operator is called: no solve, so the cut needs no halo)
+    from nksr_amd.fields.kernel_field import Segments
+    L = svh.depth
+    k_top, s = svh.level(L - 1).keys, 3 * (L - 1)
+    h = k_top.numel() // 2
+    seg2 = Segments(svh, torch.stack([k_top[0], k_top[h]]) << s, torch.stack([k_top[h], k_top[-1] + 1]) << s)
+    wp, wn = 1e4 / len(xyz), 1e2 / len(nxyz)
+    for sites in ((t(xyz), t(nxyz), t(nval)), (t(xyz), None, None), (None, t(nxyz), t(nval))):      # both sets, positions alone, normals alone
+        for segments in (None, seg2):
+            out = {}
+            for mode in ('merge', 'sort'):
+                monkeypatch.setenv('NKSR_ROW_ORDER', mode)
+                op = fld.fused_operator(*sites, wp, wn, segments=segments)
+                if op['row_format'] == 'factors':
+                    n = op['op'].depth * op['rows_total'] * 4
+                    rows = torch.cat([op['fac_vec'][:n], op['fac_pos'][:op['rows_total'] * 4]])
+                else:
+                    rows = fld.dense_rows(op).reshape(-1)
+                out[mode] = (rows.clone(), op['row_cells'].clone(), op['targets_all'].clone(), op['rows_total'], op['item_seg'], op['pad_rows'])
+            assert out['merge'][3] == out['sort'][3]
+            assert torch.equal(out['merge'][1], out['sort'][1]) and torch.equal(out['merge'][2], out['sort'][2])
+            assert torch.equal(out['merge'][0].view(torch.int32), out['sort'][0].view(torch.int32))
+            if segments is None:
+                assert all(out[m][4] is None and out[m][5] is None for m in out)
+            else:
+                assert out['merge'][3] % 256 == 0 and out['merge'][4].dtype == torch.int32
+                assert torch.equal(out['merge'][4], out['sort'][4]) and torch.equal(out['merge'][5], out['sort'][5])
 
 
 @pytest.mark.parametrize('approx', [False, True])
