@@ -305,7 +305,11 @@ double nksr_pcg_profile_survey_bytes(void);
  * Chebyshev steps on their diagonal block A_cc instead of one Jacobi step; all finer unknowns keep Jacobi.  A_cc: plain CSR
  * (nksr_assemble with col_format 2 on the hierarchy whose fine levels have n = 0, hcap = 0 and whose coarse levels are
  * re-based to offset 0), local indices.  lambda_max: largest eigenvalue of D^-1 A_cc (nksr_coarse_lambda_max, x ~1.1);
- * the polynomial targets the interval [lambda_max / ratio, lambda_max]. */
+ * the polynomial targets the interval [lambda_max / ratio, lambda_max].
+ * PRECONDITION on the plain block, relied on by every kernel that reads it and checked by none: every row holds at least its
+ * diagonal entry, and holds it as its LAST entry (cols[rowptr[j + 1] - 1] == j, vals[rowptr[j + 1] - 1] == diag[j]); the entries
+ * before it may come in any order.  The packer drops entry rowptr[j + 1] - 1 of every row unseen (the packed block has a unit
+ * diagonal), and the Chebyshev step and the power iteration clamp their loads to that entry: an empty row would read entry -1. */
 #define NKSR_PC_MAX_STEPS 16
 /* Independent diagonal blocks of one system ("segments": the chunks of a batched chunk solve -- the reference solves its
  * chunks one after the other, examples/recons_by_chunk.py:26-29; here all chunks of a rank share every launch).  The unknowns
@@ -359,6 +363,11 @@ int nksr_coarse_lambda_max_packed(const nksr_coarse_precond_t* pc, int32_t nseg,
  * over the coarse rows of every segment (`first` = unknown index of coarse row 0; the ranges below it are skipped). */
 int nksr_coarse_lambda_max(const int32_t* rowptr, const int32_t* cols, const float* vals, const float* diag, int32_t n, int iters,
                            float* work, float* lambda_out, const nksr_segments_t* segments, int32_t first, void* stream);
+/* The preconditioner by itself, exactly as nksr_pcg_solve applies it: z = p(A_cc) r for the coarse slices r, z (device, [pc->n], PCG
+ * order; pc->first is not used).  Validates pc as the solve does (1 .. NKSR_PC_MAX_STEPS steps, lambda_scale > 0, ratio > 1, the
+ * arrays of its format), writes the coefficient table of the nseg segments into pc->coef from pc->lambda / pc->gersh, then runs
+ * the `steps` Chebyshev steps in pc->work.  Asynchronous on `stream`. */
+int nksr_coarse_precond_apply(const nksr_coarse_precond_t* pc, int32_t nseg, const float* r, float* z, void* stream);
 
 /* ---- matrix-free ("fused") operator and solve: reconstruct(..., fused_mode=True), examples/recons_waymo.py:33,
  *      recons_waymo_cpu.py:58, gis_app.py:40; KernelField.solve (csrc/fused.hip).  The system matrix is never built:

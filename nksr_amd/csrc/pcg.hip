@@ -1096,6 +1096,18 @@ static void cheb_apply(const nksr_coarse_precond_t* pc, const float* r, float* z
         hipLaunchKernelGGL(k_cheb_step, dim3(nksr_blocks((int64_t)n * 64, 256)), dim3(256), 0, st, n, pc->rowptr, pc->cols, pc->vals, pc->diag,
                            (const float*)pc->coef, i, pc->row_seg, res, (const float*)d[i & 1], d[(i + 1) & 1], z, sc);
 }
+// the operator by itself, as the solve applies it to its first residual: the checks, the coefficient table, one application
+extern "C" int nksr_coarse_precond_apply(const nksr_coarse_precond_t* pc, int32_t nseg, const float* r, float* z, void* stream) {
+    if (!pc) return nksr_set_error(NKSR_ERR_ARG, "coarse preconditioner is NULL");
+    if (nseg < 1) return nksr_set_error(NKSR_ERR_ARG, "coarse preconditioner: nseg must be >= 1");
+    if (int rc = cheb_check(pc, nseg)) return rc;
+    if (!r || !z) return nksr_set_error(NKSR_ERR_ARG, "coarse preconditioner: r / z is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_cheb_coeffs, dim3(nksr_blocks(nseg, 64)), dim3(64), 0, st, nseg, pc->lambda, pc->gersh, pc->lambda_scale, pc->ratio, pc->steps, pc->coef);
+    cheb_apply(pc, r, z, nullptr, st);
+    NKSR_CHECK_LAUNCH();
+    return NKSR_OK;
+}
 
 int nksr_pcg_run(PcgOperator& A, const float* diag, int32_t M, const float* b, float* x, float tol, int max_iter, int check_every,
                  void* vector_workspace, double* info_out, hipStream_t st, const nksr_coarse_precond_t* pc, const nksr_segments_t* seg) {

@@ -205,6 +205,31 @@ def test_c_abi_argument_errors_without_a_gpu():
     hh.lv[3].n = 5
     assert lib.nksr_fused_tables(C.byref(hh), C.c_int64(0), null, null, null, null, null, null) != 0 and 'NULL' in err()
     assert lib.nksr_coarse_lambda_max(null, null, null, null, C.c_int32(5), C.c_int(8), null, null, None, C.c_int32(0), null) != 0 and 'NULL' in err()
+    # nksr_coarse_precond_apply validates like the solve: NULL pc, 1 .. NKSR_PC_MAX_STEPS steps, ratio > 1, lambda_scale > 0, NULL r / z
+    buf = (C.c_float * 256)()
+    at = C.cast(buf, C.c_void_p)
+
+    def good_pc():
+        pc = _lib.CoarsePrecondT()
+        pc.first, pc.n, pc.steps, pc.format, pc.lambda_scale, pc.ratio = 0, 4, 8, 0, 1.1, 40.0
+        for f in ('lambda_', 'rowptr', 'cols', 'vals', 'diag', 'work', 'coef'):
+            setattr(pc, f, at)
+        return pc
+    assert 'nksr_coarse_precond_apply' in _lib.EXPORTED
+    assert lib.nksr_coarse_precond_apply(None, C.c_int32(1), at, at, null) != 0 and 'NULL' in err()
+    for field, value, word in (('steps', 0, 'steps'), ('steps', _lib.PC_MAX_STEPS + 1, 'steps'), ('ratio', 1.0, 'ratio'), ('ratio', 0.5, 'ratio'),
+                               ('ratio', float('nan'), 'ratio'), ('lambda_scale', 0.0, 'lambda_scale'), ('n', 0, 'steps'), ('coef', None, 'NULL'),
+                               ('diag', None, 'NULL')):
+        pc = good_pc()
+        setattr(pc, field, value)
+        assert lib.nksr_coarse_precond_apply(C.byref(pc), C.c_int32(1), at, at, null) != 0 and word in err(), (field, value, err())
+    pc = good_pc()
+    assert lib.nksr_coarse_precond_apply(C.byref(pc), C.c_int32(1), null, at, null) != 0 and 'NULL' in err()
+    assert lib.nksr_coarse_precond_apply(C.byref(pc), C.c_int32(1), at, null, null) != 0 and 'NULL' in err()
+    assert lib.nksr_coarse_precond_apply(C.byref(pc), C.c_int32(0), at, at, null) != 0 and 'nseg' in err()
+    assert lib.nksr_coarse_precond_apply(C.byref(pc), C.c_int32(2), at, at, null) != 0 and 'row_seg' in err()      # plain block, two segments
+    pc.format = 1
+    assert lib.nksr_coarse_precond_apply(C.byref(pc), C.c_int32(1), at, at, null) != 0 and 'packed' in err()
     one = (C.c_float * 8)()
     assert lib.nksr_sdf_from_points(one, one, null, null, null, null, null, C.c_int32(0), C.c_float(1.0), C.c_float(1.0), one, C.c_int64(1), C.c_int(0),
                                     C.c_int(4), C.c_float(0.02), C.c_int(0), one, null, one, null) != 0 and 'nb_points' in err()
