@@ -105,22 +105,27 @@ int nksr_site_ranges(const int64_t* site_keys, int64_t ns, const int64_t* vox_ke
 
 /* Trilinear splat (weighted sum + weight sum) of per-point features onto the voxels of one
  * level; points must be Morton-sorted with start/end = nksr_site_ranges of that level.
- * Point encoder skip path (network.encoder, models/nksr_net.py:73). */
+ * Point encoder skip path (network.encoder, models/nksr_net.py:73).
+ * With n > 0 every array must be non-NULL (NKSR_ERR_ARG otherwise) AND the cloud must hold at least one point: the splats carry no
+ * point count and read point 0 unconditionally.  An empty cloud is the caller's case (nn/network.py returns zeros without a launch). */
 int nksr_splat_trilinear(const float* xyz_sorted, const float* feat_sorted, int C, const int32_t* start,
                          const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w,
                          float* out, float* wsum_out, void* stream);
 
 /* ---- sparse feature-hierarchy network (network.encoder / network.unet, models/nksr_net.py:73-78;
- *      csrc/nn.hip).  C = unet.f_maps = 32 (configs/default/train.yaml:17-18). --------------------- */
+ *      csrc/nn.hip).  C = unet.f_maps = 32 (configs/default/train.yaml:17-18).
+ *      Every entry below checks its arguments before any launch: with n > 0 a NULL array is NKSR_ERR_ARG (a NULL pointer would pass
+ *      the 16-byte alignment tests); the optional ones are named.  n <= 0 is NKSR_OK and touches nothing. --------------------- */
 /* per-point MLP on [local cell coordinate - 1/2 (3), orientation feature (3)]:  W1 [C,6], W2 [C,C] */
 int nksr_point_mlp(const float* xyz, const float* feat, int64_t n, float inv_w0, int C, const float* W1,
                    const float* b1, const float* W2, const float* b2, float* out, void* stream);
-/* trilinear splat-MEAN of C-channel point features onto one level (points Morton-sorted) */
+/* trilinear splat-MEAN of C-channel (1..64) point features onto one level (points Morton-sorted; at least one point, see
+ * nksr_splat_trilinear) */
 int nksr_splat_mean(const float* xyz_sorted, const float* feat_sorted, int C, const int32_t* start,
                     const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* out,
                     void* stream);
 /* 3x3x3 submanifold sparse convolution on the fp32 matrix cores: out = act(b + sum_s W[s]^T in[nbr[:,s]]
- * (+ residual)),  W [27, C, C]  in / W: 16-byte aligned (NKSR_ERR_ARG otherwise). */
+ * (+ residual)),  W [27, C, C]  in / W: 16-byte aligned (NKSR_ERR_ARG otherwise); bias / residual: optional (NULL). */
 int nksr_sparse_conv3(const float* in, const int32_t* nbr, int32_t n, int C, const float* W, const float* bias,
                       const float* residual, int relu, float* out, void* stream);
 /* Weight gradient of nksr_sparse_conv3 (training path, network.unet under autograd, models/nksr_net.py:74-78):
@@ -131,19 +136,21 @@ int nksr_conv3_wgrad(const float* in, const int32_t* nbr, int32_t n, int C, cons
 /* mean over the children (contiguous Morton range start/end in the finer level) of every voxel */
 int nksr_pool_children(const float* child_feat, const int32_t* start, const int32_t* end, int32_t n_parent, int C,
                        float* out, void* stream);
-/* out[i] = (idx[i] >= 0 ? src[idx[i]] : 0) (+ add[i]) -- hierarchy transfer / parent->child up-sampling */
+/* out[i] = (idx[i] >= 0 ? src[idx[i]] : 0) (+ add[i]) -- hierarchy transfer / parent->child up-sampling; add: optional (NULL) */
 int nksr_gather_rows(const float* src, const int32_t* idx, int64_t n, int C, const float* add, float* out, void* stream);
-/* per-voxel linear head: out [n, Cout] = in [n, 32] W^T + b */
+/* per-voxel linear head: out [n, Cout] = in [n, 32] W^T + b,  1 <= Cout <= 32; b: optional (NULL) */
 int nksr_linear(const float* in, int64_t n, int Cin, const float* W, const float* b, int Cout, float* out, void* stream);
 
 /* ---- UDF mask branch: NeuralField(svh=udf_svh, decoder=network.udf_decoder, features=feat.udf_features)
  *      .set_level_set(2 * voxel_size)  (models/nksr_net.py:124-130; configs/carla/train.yaml:8-9) ---------- */
 /* plane features of one level, out [n, 8] = (occupied, centroid offset xyz in voxel units, unit mean normal
- * xyz, 0): trilinear-weighted over the Morton-sorted points around every voxel */
+ * xyz, 0): trilinear-weighted over the Morton-sorted points around every voxel (at least one point, see nksr_splat_trilinear);
+ * NULL arrays with n > 0: NKSR_ERR_ARG */
 int nksr_splat_plane(const float* xyz_sorted, const float* normal_sorted, const int32_t* start, const int32_t* end,
                      const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* out, void* stream);
 /* unsigned plane distance decoded from the 8 voxel centres around every query (1e30 where none is
- * occupied); only_unset != 0 keeps entries already decoded at a finer level */
+ * occupied); only_unset != 0 keeps entries already decoded at a finer level.  NULL out, or NULL feat / xyz / hash table of a level
+ * that has voxels, with n > 0: NKSR_ERR_ARG */
 int nksr_udf_decode(const nksr_level_t* level, int level_index, const float* feat, const float* xyz, int64_t n,
                     float inv_w, float voxel_size, int only_unset, float* out, void* stream);
 

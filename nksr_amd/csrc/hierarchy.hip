@@ -327,6 +327,8 @@ extern "C" int nksr_splat_trilinear(const float* xyz_sorted, const float* feat_s
                                     const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w,
                                     float* out, float* wsum_out, void* stream) {
     if (C < 1 || C > 8) return nksr_set_error(NKSR_ERR_ARG, "splat supports 1..8 channels");
+    if (n <= 0) return NKSR_OK;
+    if (!xyz_sorted || !feat_sorted || !start || !end || !nbr || !ijk || !out || !wsum_out) return nksr_set_error(NKSR_ERR_ARG, "splat_trilinear: NULL arrays");
     LAUNCH1D(k_splat_trilinear, (int64_t)n * 32, stream, xyz_sorted, feat_sorted, C, start, end, nbr, ijk, n, inv_w, out, wsum_out);
     return NKSR_OK;
 }

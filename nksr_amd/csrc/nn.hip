@@ -404,6 +404,8 @@ __global__ void k_linear(const float* __restrict__ in, int64_t n, const float* _
 extern "C" int nksr_point_mlp(const float* xyz, const float* feat, int64_t n, float inv_w0, int C, const float* W1,
                               const float* b1, const float* W2, const float* b2, float* out, void* stream) {
     if (C != NN_C) return nksr_set_error(NKSR_ERR_ARG, "unet.f_maps must be %d", NN_C);
+    if (n <= 0) return NKSR_OK;
+    if (!xyz || !feat || !W1 || !b1 || !W2 || !b2 || !out) return nksr_set_error(NKSR_ERR_ARG, "point_mlp: NULL arrays");
     if ((uintptr_t)out & 15) return nksr_set_error(NKSR_ERR_ARG, "point_mlp: out must be 16-byte aligned (rows leave as 16-byte pieces)");
     LAUNCH1D(k_point_mlp, n, stream, xyz, feat, n, inv_w0, W1, b1, W2, b2, out);
     return NKSR_OK;
@@ -412,7 +414,9 @@ extern "C" int nksr_splat_mean(const float* xyz_sorted, const float* feat_sorted
                                const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* out,
                                void* stream) {
     if (C < 1 || C > 64) return nksr_set_error(NKSR_ERR_ARG, "splat_mean supports 1..64 channels");
-    if (C == 32 && n > 0) {
+    if (n <= 0) return NKSR_OK;
+    if (!xyz_sorted || !feat_sorted || !start || !end || !nbr || !ijk || !out) return nksr_set_error(NKSR_ERR_ARG, "splat_mean: NULL arrays");
+    if (C == 32) {
         hipLaunchKernelGGL(k_splat_mean32, dim3(nksr_blocks((int64_t)n * 32, 256)), dim3(256), 0, (hipStream_t)stream, xyz_sorted, feat_sorted, start, end,
                            nbr, ijk, n, inv_w, out);
         NKSR_CHECK_LAUNCH();
@@ -425,6 +429,7 @@ extern "C" int nksr_sparse_conv3(const float* in, const int32_t* nbr, int32_t n,
                                  const float* residual, int relu, float* out, void* stream) {
     if (C != NN_C) return nksr_set_error(NKSR_ERR_ARG, "unet.f_maps must be %d", NN_C);
     if (n <= 0) return NKSR_OK;
+    if (!in || !nbr || !W || !out) return nksr_set_error(NKSR_ERR_ARG, "sparse_conv3: NULL arrays");      // (bias / residual: optional)
     if (((uintptr_t)in | (uintptr_t)W) & 15) return nksr_set_error(NKSR_ERR_ARG, "sparse_conv3: in and W must be 16-byte aligned (16-byte row / weight loads)");
     hipLaunchKernelGGL(k_sparse_conv3, dim3(nksr_blocks(n, 128)), dim3(256), 0, (hipStream_t)stream, in, nbr, n, W, bias,
                        residual, relu, out);
@@ -433,13 +438,18 @@ extern "C" int nksr_sparse_conv3(const float* in, const int32_t* nbr, int32_t n,
 }
 extern "C" int nksr_pool_children(const float* child_feat, const int32_t* start, const int32_t* end, int32_t n_parent, int C,
                                   float* out, void* stream) {
+    if (C < 1) return nksr_set_error(NKSR_ERR_ARG, "pool_children: C must be positive");
+    if (n_parent <= 0) return NKSR_OK;
+    if (!child_feat || !start || !end || !out) return nksr_set_error(NKSR_ERR_ARG, "pool_children: NULL arrays");
     LAUNCH1D(k_pool_children, (int64_t)n_parent * C, stream, child_feat, start, end, n_parent, C, out);
     return NKSR_OK;
 }
 extern "C" int nksr_gather_rows(const float* src, const int32_t* idx, int64_t n, int C, const float* add, float* out,
                                 void* stream) {
+    if (C < 1) return nksr_set_error(NKSR_ERR_ARG, "gather_rows: C must be positive");
+    if (n <= 0) return NKSR_OK;
+    if (!src || !idx || !out) return nksr_set_error(NKSR_ERR_ARG, "gather_rows: NULL arrays");      // (add: optional)
     if (C == NN_C && !(((uintptr_t)src | (uintptr_t)add | (uintptr_t)out) & 15)) {
-        if (n <= 0) return NKSR_OK;
         hipLaunchKernelGGL(k_gather_rows32, dim3(nksr_blocks(n * 8, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(src), idx, n,
                            reinterpret_cast<const float4*>(add), reinterpret_cast<float4*>(out));
         NKSR_CHECK_LAUNCH();
@@ -451,22 +461,29 @@ extern "C" int nksr_gather_rows(const float* src, const int32_t* idx, int64_t n,
 extern "C" int nksr_linear(const float* in, int64_t n, int Cin, const float* W, const float* b, int Cout, float* out,
                            void* stream) {
     if (Cin != NN_C || Cout < 1 || Cout > NN_C) return nksr_set_error(NKSR_ERR_ARG, "linear head expects Cin=%d, Cout<=%d", NN_C, NN_C);
+    if (n <= 0) return NKSR_OK;
+    if (!in || !W || !out) return nksr_set_error(NKSR_ERR_ARG, "linear: NULL arrays");      // (b: optional)
     LAUNCH1D(k_linear, n * Cout, stream, in, n, W, b, Cout, out);
     return NKSR_OK;
 }
 
 extern "C" int nksr_splat_plane(const float* xyz_sorted, const float* normal_sorted, const int32_t* start, const int32_t* end,
                                 const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* out, void* stream) {
+    if (n <= 0) return NKSR_OK;
+    if (!xyz_sorted || !normal_sorted || !start || !end || !nbr || !ijk || !out) return nksr_set_error(NKSR_ERR_ARG, "splat_plane: NULL arrays");
     LAUNCH1D(k_splat_plane, n, stream, xyz_sorted, normal_sorted, start, end, nbr, ijk, n, inv_w, out);
     return NKSR_OK;
 }
 extern "C" int nksr_udf_decode(const nksr_level_t* level, int level_index, const float* feat, const float* xyz, int64_t n,
                                float inv_w, float voxel_size, int only_unset, float* out, void* stream) {
     if (!level) return nksr_set_error(NKSR_ERR_ARG, "null level");
+    if (n <= 0) return NKSR_OK;
+    if (!out) return nksr_set_error(NKSR_ERR_ARG, "udf_decode: NULL arrays");
     if (level->n <= 0) {
         if (!only_unset && n > 0) { LAUNCH1D(k_fill_f32, n, stream, out, n, NKSR_UDF_FAR); }
         return NKSR_OK;
     }
+    if (!feat || !xyz || !level->hkeys || !level->hvals) return nksr_set_error(NKSR_ERR_ARG, "udf_decode: NULL arrays");
     LAUNCH1D(k_udf_decode, n, stream, *level, feat, xyz, n, inv_w, voxel_size, level_index, only_unset, out);
     return NKSR_OK;
 }

@@ -102,6 +102,8 @@ def site_ranges(site_keys, grid, shift_level):
 def splat_trilinear(grid, d, inv_w0, site_keys, xyz_sorted, feat_sorted):
     """Weighted SUM (and weight sum) of <= 8-channel features splatted onto level-d ``grid``."""
     n, C_ = grid.num_voxels, feat_sorted.shape[1]
+    if xyz_sorted.shape[0] == 0:      # the kernels carry no point count and read point 0 unconditionally: no launch on an empty cloud
+        return torch.zeros((n, C_), dtype=torch.float32, device=grid.device), torch.zeros(n, dtype=torch.float32, device=grid.device)
     st, en = site_ranges(site_keys, grid, d)
     out = torch.empty((n, C_), dtype=torch.float32, device=grid.device)
     ws = torch.empty(n, dtype=torch.float32, device=grid.device)
@@ -112,6 +114,8 @@ def splat_trilinear(grid, d, inv_w0, site_keys, xyz_sorted, feat_sorted):
 
 def splat_mean(grid, d, inv_w0, site_keys, xyz_sorted, feat_sorted):
     n, C_ = grid.num_voxels, feat_sorted.shape[1]
+    if xyz_sorted.shape[0] == 0:      # (as splat_trilinear)
+        return torch.zeros((n, C_), dtype=torch.float32, device=grid.device)
     st, en = site_ranges(site_keys, grid, d)
     out = torch.empty((n, C_), dtype=torch.float32, device=grid.device)
     call('nksr_splat_mean', ptr(xyz_sorted), ptr(feat_sorted), C_, ptr(st), ptr(en), ptr(grid.nbr), ptr(grid.ijk), n,
@@ -122,6 +126,8 @@ def splat_mean(grid, d, inv_w0, site_keys, xyz_sorted, feat_sorted):
 def splat_plane(grid, d, inv_w0, site_keys, xyz_sorted, normal_sorted):
     """Plane features [n, 8] = (occupied, centroid offset, unit mean normal, 0) of level-d ``grid``."""
     n = grid.num_voxels
+    if xyz_sorted.shape[0] == 0:      # (as splat_trilinear): no voxel is occupied
+        return torch.zeros((n, 8), dtype=torch.float32, device=grid.device)
     st, en = site_ranges(site_keys, grid, d)
     out = torch.empty((n, 8), dtype=torch.float32, device=grid.device)
     call('nksr_splat_plane', ptr(xyz_sorted), ptr(normal_sorted), ptr(st), ptr(en), ptr(grid.nbr), ptr(grid.ijk), n,

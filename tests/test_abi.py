@@ -235,6 +235,71 @@ def test_c_abi_argument_errors_without_a_gpu():
                                     C.c_int(4), C.c_float(0.02), C.c_int(0), one, null, one, null) != 0 and 'nb_points' in err()
     assert lib.nksr_sdf_from_points(one, one, null, null, null, null, null, C.c_int32(0), C.c_float(1.0), C.c_float(1.0), one, C.c_int64(1), C.c_int(8),
                                     C.c_int(4), C.c_float(0.0), C.c_int(0), one, null, one, null) != 0 and 'stdv' in err()
+    # the network kernels (csrc/nn.hip, nksr_splat_trilinear): with n > 0 a NULL array, a channel count the kernel is not built for
+    # or a misaligned in / W / out is an argument error before any launch; n <= 0 is a no-op
+    big = (C.c_float * 4096)()
+    a16 = (C.addressof(big) + 15) & ~15            # a 16-byte aligned host address (never dereferenced: every call below fails first)
+    A, odd, Z = C.c_void_p(a16), C.c_void_p(a16 + 4), None
+    f1 = C.c_float(1.0)
+
+    def each_null(fn, args, optional=()):
+        """``fn(*args)`` must fail with 'NULL' for every pointer argument set to NULL alone (the optional ones excepted)."""
+        where = [k for k, a in enumerate(args) if a is A]
+        assert where
+        for k in where:
+            if k in optional:
+                continue
+            bad = list(args)
+            bad[k] = Z
+            assert fn(*bad) != 0 and 'NULL' in err(), (fn.__name__, k, err())
+
+    each_null(lib.nksr_sparse_conv3, [A, A, 5, 32, A, A, A, 1, A, Z], optional=(5, 6))
+    assert lib.nksr_sparse_conv3(A, A, 5, 16, A, A, Z, 1, A, Z) != 0 and 'f_maps' in err()
+    assert lib.nksr_sparse_conv3(odd, A, 5, 32, A, A, Z, 1, A, Z) != 0 and 'aligned' in err()
+    assert lib.nksr_sparse_conv3(A, A, 5, 32, odd, A, Z, 1, A, Z) != 0 and 'aligned' in err()
+    assert lib.nksr_sparse_conv3(Z, Z, 0, 32, Z, Z, Z, 1, Z, Z) == 0
+    each_null(lib.nksr_conv3_wgrad, [A, A, 5, 32, A, A, Z])
+    assert lib.nksr_conv3_wgrad(A, A, 5, 31, A, A, Z) != 0 and 'f_maps' in err()
+    each_null(lib.nksr_point_mlp, [A, A, 5, f1, 32, A, A, A, A, A, Z])
+    assert lib.nksr_point_mlp(A, A, 5, f1, 33, A, A, A, A, A, Z) != 0 and 'f_maps' in err()
+    assert lib.nksr_point_mlp(A, A, 5, f1, 32, A, A, A, A, odd, Z) != 0 and 'aligned' in err()
+    assert lib.nksr_point_mlp(Z, Z, 0, f1, 32, Z, Z, Z, Z, Z, Z) == 0
+    for ch in (32, 5):                              # the half-wave kernel and the generic one
+        each_null(lib.nksr_splat_mean, [A, A, ch, A, A, A, A, 3, f1, A, Z])
+    for ch in (0, 65):
+        assert lib.nksr_splat_mean(A, A, ch, A, A, A, A, 3, f1, A, Z) != 0 and 'channels' in err()
+    assert lib.nksr_splat_mean(Z, Z, 32, Z, Z, Z, Z, 0, f1, Z, Z) == 0
+    each_null(lib.nksr_splat_trilinear, [A, A, 3, A, A, A, A, 3, f1, A, A, Z])
+    assert lib.nksr_splat_trilinear(A, A, 0, A, A, A, A, 3, f1, A, A, Z) != 0 and 'channels' in err()
+    each_null(lib.nksr_splat_plane, [A, A, A, A, A, A, 3, f1, A, Z])
+    for ch in (32, 5):
+        each_null(lib.nksr_pool_children, [A, A, A, 3, ch, A, Z])
+    assert lib.nksr_pool_children(A, A, A, 3, 0, A, Z) != 0 and 'positive' in err()
+    for ch, src in ((32, A), (8, A), (32, odd)):    # the 16-byte path, the generic one, and the generic one through a misaligned source
+        for k, word in ((0, 'NULL'), (1, 'NULL'), (5, 'NULL')):
+            args = [src, A, 3, ch, A, A, Z]
+            args[k] = Z
+            assert lib.nksr_gather_rows(*args) != 0 and word in err(), (ch, k, err())
+    assert lib.nksr_gather_rows(A, A, 3, 0, Z, A, Z) != 0 and 'positive' in err()
+    each_null(lib.nksr_linear, [A, 3, 32, A, A, 4, A, Z], optional=(4,))
+    for cin, cout in ((32, 33), (32, 0), (16, 4)):
+        assert lib.nksr_linear(A, 3, cin, A, A, cout, A, Z) != 0 and 'Cout' in err()
+    lv = _lib.LevelT()
+    lv.n, lv.hcap = 4, 8
+    lv.hkeys, lv.hvals = A, A
+    assert lib.nksr_udf_decode(None, 0, A, A, 3, f1, f1, 0, A, Z) != 0 and 'null level' in err()
+    for k in (2, 3, 8):
+        args = [C.byref(lv), 0, A, A, 3, f1, f1, 0, A, Z]
+        args[k] = Z
+        assert lib.nksr_udf_decode(*args) != 0 and 'NULL' in err(), (k, err())
+    for f in ('hkeys', 'hvals'):
+        lv2 = _lib.LevelT()
+        lv2.n, lv2.hcap, lv2.hkeys, lv2.hvals = 4, 8, A, A
+        setattr(lv2, f, None)
+        assert lib.nksr_udf_decode(C.byref(lv2), 0, A, A, 3, f1, f1, 0, A, Z) != 0 and 'NULL' in err(), f
+    empty = _lib.LevelT()                            # a level without voxels only fills `out`: that one is still checked
+    assert lib.nksr_udf_decode(C.byref(empty), 0, Z, Z, 3, f1, f1, 0, Z, Z) != 0 and 'NULL' in err()
+    assert lib.nksr_udf_decode(C.byref(empty), 0, Z, Z, 3, f1, f1, 1, A, Z) == 0       # only_unset: nothing to do, nothing launched
     assert lib.nksr_assemble_split_bytes(C.byref(h), C.c_int64(10 ** 6)) == 0           # no voxels: nothing to split
     with __import__('pytest').raises(RuntimeError):
         _lib.call('nksr_pack_cols21', null, 100, null, null)
