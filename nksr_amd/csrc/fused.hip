@@ -274,6 +274,22 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FAC ? 3 : (D <= 4 ? 6 : 5))))
     __shared__ float4 fv[FAC ? D * RS : 1], fp[FAC ? RS : 1];
     for (int i = threadIdx.x; i < CAP0 + CAP1; i += FZ_BLOCK) stf[i] = 0;
     const int W0 = __builtin_amdgcn_readfirstlane(A.item_begin[blockIdx.x * FZ_HW]);
+    if (__builtin_amdgcn_readfirstlane(A.item_begin[(blockIdx.x + 1) * FZ_HW]) == W0) {
+        // A workgroup WITHOUT rows: one unit (a cell with hundreds of sites) covers its whole 256-row window and belongs to the
+        // workgroup it starts in.  k_fz_block_counts gives a cell one partial block per workgroup from its first to its last, this
+        // one included, k_fz_cellsum adds them all, and the workspace has no initial value: the blocks nobody fills are written
+        // here, as zeros.  They belong to the coarse cells of the row before this workgroup (the covering unit's) that go on after it.
+        if (W0 > 0 && threadIdx.x < 32 * D) {
+            const int d = threadIdx.x >> 5;
+            const int c = A.row_cells[(int64_t)d * A.rows_total + W0 - 1];
+            if (c >= 0 && A.nbr32[(int64_t)c * 32 + 29] >= W0) {
+                const int64_t blk = (int64_t)A.nbr32[(int64_t)c * 32 + 27] + blockIdx.x;
+                part[blk * 32 + (threadIdx.x & 31)] = 0.f;
+                if (MODE == 1) part2[blk * 32 + (threadIdx.x & 31)] = 0.f;
+            }
+        }
+        return;
+    }
     if (FAC) {
         // the records of the workgroup's rows [W0, W1): (D + 1) coalesced bursts, all loads before the first store.  Rows past the
         // last one (a trip reads four) are zeroed: never used (their t is 0) but they must be finite

@@ -39,6 +39,35 @@ def check(name, measured, bound):
         assert measured <= bound, '%s: measured %.3e > bound %.3e' % (name, measured, bound)
 
 
+def field_inputs(xyz, dev, K=4, H=16, depth=4, init_scale=0.5, seed=0, random_feats=True):
+    """The same hierarchy (cells of the points ``xyz`` and their 26 neighbours), features and interpolators on both sides:
+    (oracle hierarchy, SparseFeatureHierarchy, features per level, oracle interpolators, network)."""
+    import torch
+    import nksr_amd
+    from nksr_amd import configs
+    from nksr_amd.nn.network import NKSRNetwork
+    from oracle import hierarchy, kernel
+    hp = configs.get_hparams('ks', kernel_dim=K, interpolator={'n_hidden': 2, 'hidden_dim': H}, tree_depth=depth,
+                             interpolator_init_scale=init_scale)
+    net = NKSRNetwork(hp)
+    rs = np.random.RandomState(seed + 1)
+    for it in net.interpolators:  # non-trivial biases so every MLP branch is exercised
+        it.b1.data = torch.from_numpy(rs.randn(H).astype(np.float32) * 0.2)
+        it.b2.data = torch.from_numpy(rs.randn(H).astype(np.float32) * 0.2)
+        it.b3.data = torch.from_numpy(rs.randn(K).astype(np.float32) * 0.05)
+    oh = hierarchy.Hierarchy(0.1, depth).build_point_neighborhood(xyz)
+    svh = nksr_amd.SparseFeatureHierarchy(0.1, depth, dev).build_point_neighborhood(torch.from_numpy(xyz).to(dev))
+    feats = []
+    for L in oh.levels:
+        f = np.zeros((L.n, K), np.float32)
+        f[:, 0] = 1
+        if random_feats:
+            f += rs.randn(L.n, K).astype(np.float32) * 0.3
+        feats.append(f)
+    ointerps = [kernel.Interpolator(*[p.detach().numpy() for p in (i.W1, i.b1, i.W2, i.b2, i.W3, i.b3)]) for i in net.interpolators]
+    return oh, svh, feats, ointerps, net
+
+
 def check_alpha(name, alpha_hip, ofl, tol):
     """Converged coefficient vectors.  The multi-level basis is redundant (a coarse B-spline is a combination of fine
     ones wherever the fine level exists), so A has near-null directions held only by reg*I: two solves that both reach

@@ -17,31 +17,10 @@ def _dev():
 
 def _setup(kind='sphere', n=3000, vs=0.05, K=4, H=16, depth=4, init_scale=0.5, seed=0, random_feats=True):
     """Same hierarchy / features / interpolators on both sides."""
-    import nksr_amd
-    from nksr_amd import configs
-    from nksr_amd.nn.network import NKSRNetwork
-    from oracle import hierarchy, kernel
     xyz, nrm = make_cloud(kind, n, 0.005, seed)
     scale = 0.1 / vs
     xyz = (xyz * np.float32(scale)).astype(np.float32)
-    hp = configs.get_hparams('ks', kernel_dim=K, interpolator={'n_hidden': 2, 'hidden_dim': H}, tree_depth=depth,
-                             interpolator_init_scale=init_scale)
-    net = NKSRNetwork(hp)
-    rs = np.random.RandomState(seed + 1)
-    for it in net.interpolators:  # non-trivial biases so every MLP branch is exercised
-        it.b1.data = torch.from_numpy(rs.randn(H).astype(np.float32) * 0.2)
-        it.b2.data = torch.from_numpy(rs.randn(H).astype(np.float32) * 0.2)
-        it.b3.data = torch.from_numpy(rs.randn(K).astype(np.float32) * 0.05)
-    oh = hierarchy.Hierarchy(0.1, depth).build_point_neighborhood(xyz)
-    svh = nksr_amd.SparseFeatureHierarchy(0.1, depth, _dev()).build_point_neighborhood(torch.from_numpy(xyz).to(_dev()))
-    feats = []
-    for L in oh.levels:
-        f = np.zeros((L.n, K), np.float32)
-        f[:, 0] = 1
-        if random_feats:
-            f += rs.randn(L.n, K).astype(np.float32) * 0.3
-        feats.append(f)
-    ointerps = [kernel.Interpolator(*[p.detach().numpy() for p in (i.W1, i.b1, i.W2, i.b2, i.W3, i.b3)]) for i in net.interpolators]
+    oh, svh, feats, ointerps, net = pu.field_inputs(xyz, _dev(), K=K, H=H, depth=depth, init_scale=init_scale, seed=seed, random_feats=random_feats)
     return xyz, nrm, oh, svh, feats, ointerps, net
 
 
