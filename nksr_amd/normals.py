@@ -16,7 +16,7 @@ from .neighbours import PointGrid, choose_cell_size
 
 
 class TooFewPoints(RuntimeError):
-    """Fewer points than the neighbourhood size: chunk mode treats such a chunk as empty (nksr_amd/chunking.py)."""
+    """Fewer points than the neighbourhood size: chunk mode treats such a chunk as empty (nksr_amd/chunking/driver.py)."""
 
 
 def knn_pca(xyz, knn):

@@ -27,7 +27,7 @@ class Reconstructor:
         self.chunk_tmp_device = self.device
         self.timing = {}
         self.sync_timing = False   # insert stream syncs so that per-stage wall times are exact
-        # chunk mode: ALL chunks of a rank are solved as one block-diagonal system (nksr_amd/chunking.py); chunk_batch_points caps the
+        # chunk mode: ALL chunks of a rank are solved as one block-diagonal system (nksr_amd/chunking/); chunk_batch_points caps the
         # points (band included) of one such batch.  None = automatic: the batches follow the FREE device memory (~4.5 KB of HBM per solved
         # point at tree_depth 5; 70 % of what is free + what torch's allocator holds unused -- NKSR_FREE_HBM_GB overrides the free figure --,
         # at most 2^25 points).  Results do not depend on it.
@@ -53,7 +53,7 @@ class Reconstructor:
 
     # ---- one chunk: hierarchy -> features -> kernel solve -> mask -------------------------------------
     def _reconstruct_single(self, xyz, normal, approx_kernel_grad, solver_max_iter, solver_tol, fused_mode, chunks=None):
-        """``chunks`` = (ids, key_lo, key_hi, frame): the cloud is a batch of chunks in the exploded frame (nksr_amd/chunking.py) -- one
+        """``chunks`` = (ids, key_lo, key_hi, frame): the cloud is a batch of chunks in the exploded frame (nksr_amd/chunking/) -- one
         hierarchy, one network pass, ONE block-diagonal solve whose diagonal blocks (segments) are the chunks; every chunk keeps
         the solver weights of its own point / normal-site counts (models/nksr_net.py:103-111)."""
         from . import ops
