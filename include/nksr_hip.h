@@ -75,7 +75,8 @@ int nksr_cell_footprint_keys(const int64_t* cell_keys, int64_t nc, int level, in
 int nksr_bbox(const float* xyz, int64_t n, float* work, float* out6, void* stream);
 int64_t nksr_bbox_work_floats(void);
 /* The same key streams (xyz != NULL: nksr_splat_keys; cell_keys != NULL: nksr_cell_footprint_keys; exactly one of them) with the
- * duplicates inside each workgroup's run of Morton-ordered elements removed (LDS hash set): the multiset differs, the SET of keys
+ * duplicates inside each workgroup's range of Morton-ordered elements (several thousand of them) mostly removed (LDS hash set,
+ * emitted and cleared when it fills up and at the end of the range): the multiset differs, the SET of keys
  * is the same, so sort + unique behind it give the identical level.  keys_out: room for n * (8 | 27) keys; *count_out (device)
  * = number of keys written, in no particular order.  mode 2 (cell_keys, level 0): the corner keys of nksr_cell_corner_keys;
  * mode 3 (cell_keys, level 0): cell_keys IS the stream (n non-negative keys, e.g. the edge keys of nksr_mc_emit). */
@@ -394,8 +395,10 @@ typedef struct {
     const int32_t* multi;      /* [n_multi] the cells with partial blocks (cells whose rows span several 256-row workgroups of the sweep):
                                 * first the n_big cells with more than 16 blocks (one workgroup each in the per-cell sum), then the others */
     int64_t nblocks;           /* offsets[M]                                                                                 */
-    uint64_t* nnz_counter;     /* device counter or NULL: nksr_fused_rhs_diag leaves the non-zero slots of rows_all here = the
-                                * stored entries of G and Q (roofline accounting) */
+    uint64_t* nnz_counter;     /* device array of nksr_fused_count_words(rows_total) words or NULL: nksr_fused_rhs_diag leaves the non-zero
+                                * slots of rows_all in word 0 = the stored entries of G and Q (roofline accounting).
+                                * Words 1 .. are scratch without an initial value: one count per workgroup of the sweep (plain
+                                * stores), added into word 0 afterwards -- the sweep shares no word between its workgroups */
     void* workspace;           /* nksr_fused_workspace_bytes(nblocks, M)                                                     */
     float* cell_sums;          /* [27, M] per-cell block sums, slot-major, ZERO-INITIALISED by the caller (cells without rows are never written) */
     const int32_t* item_seg;   /* batched chunks (nksr_segments_t), both or neither: [ceil(rows_total / 32) + 1] segment of every 32-row window
@@ -418,6 +421,7 @@ typedef struct {
  * nksr_fused_block_counts: span_out [3, M] (first / last row of every cell, -1 = none; first workgroup), item_begin_out [nksr_fused_item_entries],
  * counts_out [M + 1] (0 or k; last entry 0) -> exclusive scan = offsets -> nksr_fused_tables (nbr32_out [M, 32], nbrT_out [27, M]). */
 int64_t nksr_fused_item_entries(int64_t rows_total);
+int64_t nksr_fused_count_words(int64_t rows_total);   /* words of nksr_fused_op_t.nnz_counter: the total + one per workgroup of the sweep */
 int nksr_fused_block_counts(int32_t depth, int32_t M, int64_t rows_total, const int32_t* row_cells, int32_t* span_out, int32_t* item_begin_out,
                             int32_t* counts_out, void* stream);
 int nksr_fused_tables(const nksr_hier_t* h, int64_t rows_total, const int32_t* item_begin, const int32_t* offsets, const int32_t* span,

@@ -33,6 +33,8 @@
 #define FZ_WG_ROWS (FZ_RC * FZ_HW)         // 256 consecutive rows per workgroup
 #define FZ_STAGE0 96                       // level-0 / level-1 cells of a workgroup whose final blocks are staged in LDS (a workgroup holds
 #define FZ_STAGE1 32                       // ~64 / ~8 of them at four rows per level-0 cell; more than fit are written word by word)
+#define FZ_STAGE0_SETUP 64                 // the same for the set-up pass (MODE 1), which stages the blocks of b AND of the diagonal
+#define FZ_STAGE1_SETUP 16
 
 // Round 4 -- where the blocks go.  A cell's block P[c][27] is final as soon as all rows of the cell have been seen.  Rounds 2-3
 // wrote one partial block per 32-row item a cell touches, summed them in a second pass (k_fz_cellsum: 15 % of the cells had two
@@ -159,7 +161,8 @@ struct FusedArgs {               // uniform scalars and base pointers only
     int n_multi, n_big, M, depth;
     int hw_total;                // items (32-row windows of the row list)
     int64_t rows_total, nblocks;
-    unsigned long long* nnz_counter;   // the set-up pass (MODE 1) adds the non-zero slots it sees (may be NULL)
+    unsigned long long* nnz_counter;   // the set-up pass (MODE 1) leaves the non-zero slots of workgroup w in word 1 + w (plain stores:
+                                       // no shared word); k_fz_count_sum adds them into word 0 (may be NULL)
     const int32_t* item_seg;     // [hw_total] segment of every 32-row item, [M] segment of every unknown (batched chunks; may be NULL)
     const int32_t* unknown_seg;
     const int* seg_done;         // device flags of the PCG: segment c finished <=> seg_done[c * seg_stride] != 0 (may be NULL)
@@ -264,10 +267,13 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FAC ? 3 : (D <= 4 ? 6 : 5))))
     __shared__ int xbase[FZ_HW][D];                                  // block base of the current cell of every level
     // final blocks of the workgroup's level-0 / level-1 cells, staged so that they leave slot-major in contiguous runs (lane = cell):
     // written word by word, 27 different lines per block, the per-cell sums cost the sweep 130 us of partial-line writes
-    constexpr int CAP0 = FZ_STAGE0, CAP1 = D > 1 ? FZ_STAGE1 : 1;
+    // (the set-up pass stages two arrays per block: at 96 / 32 blocks its 49.4 KB let three workgroups onto a CU, at 64 / 16 -- 38.9 KB --
+    // four.  With the count's atomic in the way that bought nothing, 15.4 against 14.8 ms (round 4); without it 11.4 against 12.6 ms)
+    constexpr int CAP0 = MODE == 1 ? FZ_STAGE0_SETUP : FZ_STAGE0, CAP1 = D > 1 ? (MODE == 1 ? FZ_STAGE1_SETUP : FZ_STAGE1) : 1;
     __shared__ float st0[CAP0 * 27], st1[CAP1 * 27];
     __shared__ float st0b[MODE == 1 ? CAP0 * 27 : 1], st1b[MODE == 1 ? CAP1 * 27 : 1];
     __shared__ int stf[CAP0 + CAP1];
+    __shared__ int wnnz[MODE == 1 ? FZ_BLOCK / 64 : 1];              // MODE 1: the non-zero slots every wavefront saw
     static_assert(!FAC || U == 4, "a normal site is one trip of four rows");
     // (+ four overflow slots per half-wave: the records of a trip past the staged window are copied there first)
     constexpr int RS = FZ_RCAP + 4 * FZ_HW;
@@ -288,6 +294,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FAC ? 3 : (D <= 4 ? 6 : 5))))
                 if (MODE == 1) part2[blk * 32 + (threadIdx.x & 31)] = 0.f;
             }
         }
+        if (MODE == 1 && A.nnz_counter && threadIdx.x == 0) A.nnz_counter[1 + blockIdx.x] = 0;     // (its entry has no initial value either)
         return;
     }
     if (FAC) {
@@ -578,10 +585,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FAC ? 3 : (D <= 4 ? 6 : 5))))
 #pragma unroll
     for (int d = 1; d < D; ++d)
         if (have[d]) emit(d, __shfl(cells[d], pos, 32), P[d], P2[MODE == 1 ? d : 0]);
+    // the count leaves as ONE plain store per workgroup (round 7: an atomicAdd per wavefront on one word -- 1.09 M of them in the
+    // scene's sweep -- ran at the rate the memory system serialises them)
     if (MODE == 1 && A.nnz_counter) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) nnz += __shfl_xor(nnz, o);
-        if ((threadIdx.x & 63) == 0 && nnz) atomicAdd(A.nnz_counter, (unsigned long long)nnz);           // integer: order-free
+        if ((threadIdx.x & 63) == 0) wnnz[MODE == 1 ? threadIdx.x >> 6 : 0] = nnz;
     }
     // ---- coarse cells that cross item boundaries inside this workgroup: the LAST item of the workgroup that holds a piece of the cell
     // adds the pieces in item order.  A cell that lies inside the workgroup is final; one that reaches into other workgroups leaves
@@ -589,6 +598,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(FAC ? 3 : (D <= 4 ? 6 : 5))))
     // piece of cell c <=> one of its two entries names c; a cell began in the item that holds it as its LAST cell (entry 1); items
     // may be empty (a long unit covers their window).
     __syncthreads();
+    if (MODE == 1 && A.nnz_counter && threadIdx.x == 0) {
+        unsigned long long tot = 0;
+#pragma unroll
+        for (int q = 0; q < FZ_BLOCK / 64; ++q) tot += (unsigned long long)wnnz[MODE == 1 ? q : 0];
+        A.nnz_counter[1 + blockIdx.x] = tot;
+    }
 #pragma unroll
     for (int d = 1; d < D; ++d)
 #pragma unroll
@@ -753,6 +768,19 @@ __global__ void __launch_bounds__(256) k_fz_gather(FusedArgs A, int per_xcd, con
     const float r = ((r9[0] + r9[1]) + r9[2]) + ((r9[3] + r9[4]) + r9[5]) + ((r9[6] + r9[7]) + r9[8]);
     y[j] = r + (MODE == 0 ? reg * x[j] : (MODE == 2 ? reg : 0.f));
 }
+// nnz_counter[0] += the per-workgroup counts of the set-up sweep (integers: order-free; one add per FZ_CS_PER entries)
+#define FZ_CS_PER 4096
+__global__ void __launch_bounds__(256) k_fz_count_sum(unsigned long long* __restrict__ counter, int nwg) {
+    __shared__ unsigned long long wsum[4];
+    unsigned long long v = 0;
+    const int i0 = blockIdx.x * FZ_CS_PER, i1 = i0 + FZ_CS_PER < nwg ? i0 + FZ_CS_PER : nwg;
+    for (int i = i0 + threadIdx.x; i < i1; i += 256) v += counter[1 + i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(counter, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+}
 static void fz_gather_dims(int M, dim3& grid, int& per_xcd) {
     per_xcd = ((M + 7) / 8 + 255) / 256 * 256;                       // whole workgroups
     grid = dim3((unsigned)(per_xcd / 256 * 8));
@@ -778,6 +806,7 @@ static FusedWork fz_carve(const nksr_fused_op_t* op) {
 static int fz_items(int64_t rows_total) { return (int)((rows_total + FZ_RC - 1) / FZ_RC); }
 static int fz_nwg(int64_t rows_total) { return (fz_items(rows_total) + FZ_HW - 1) / FZ_HW; }
 extern "C" int64_t nksr_fused_item_entries(int64_t rows_total) { return (int64_t)fz_nwg(rows_total) * FZ_HW + 1; }
+extern "C" int64_t nksr_fused_count_words(int64_t rows_total) { return (int64_t)fz_nwg(rows_total) + 1; }
 
 extern "C" int nksr_fused_block_counts(int32_t depth, int32_t M, int64_t rows_total, const int32_t* row_cells, int32_t* span_out,
                                        int32_t* item_begin_out, int32_t* counts_out, void* stream) {
@@ -899,6 +928,10 @@ extern "C" int nksr_fused_rhs_diag(const nksr_fused_op_t* op, float reg, float* 
     if (A.nnz_counter) (void)hipMemsetAsync(A.nnz_counter, 0, sizeof(unsigned long long), st);
     NKSR_CHECK_HIP(hipMemsetAsync(w.ct2, 0, (size_t)A.M * 27 * sizeof(float), st));
     fz_sweep<1>(A, nof, w, nod, st);
+    if (A.nnz_counter && A.hw_total > 0) {
+        const int nwg = fz_nwg(A.rows_total);
+        hipLaunchKernelGGL(k_fz_count_sum, dim3(nksr_blocks(nwg, FZ_CS_PER)), dim3(256), 0, st, A.nnz_counter, nwg);
+    }
     if (b_out) {
         fz_cellsum(A, w.part, w.ct, nod, st);
         hipLaunchKernelGGL((k_fz_gather<1>), gg, dim3(256), 0, st, A, per_xcd, (const float*)w.ct, nof, reg, b_out, nod);

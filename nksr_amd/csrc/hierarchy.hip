@@ -406,70 +406,100 @@ extern "C" int64_t nksr_bbox_work_floats(void) { return (int64_t)BB_BLOCKS * 6; 
 // Points and cells arrive in Morton order, so the 8 / 27 keys of consecutive elements repeat each other several times over: a
 // workgroup inserts the keys of its elements into an LDS hash set and emits the distinct ones (order within the stream is free:
 // the caller sorts it).  The level-0 streams shrink 4-7x, and so do the radix sort and the unique pass behind them.
+//
+// A workgroup owns a contiguous RANGE of `bpw` batches of `epb` elements (a batch: at most DD_BATCH keys) and inserts them batch by
+// batch into the same set; the set is emitted -- one ticket, a returning atomicAdd on the stream's counter, behind which the whole
+// workgroup waits -- and cleared only when the next batch might not fit (more than DD_FLUSH occupied slots) and at the end of the
+// range.  One ticket per batch (40-80 k workgroups of a 10-20 M-point stream on one word) ran at the rate the memory system
+// serialises returning atomics, ~88 per us, several times the kernel's own work; neighbouring batches also share most of their
+// keys, so a set that lives across batches drops more repeats.
 #define DD_SLOTS 4096
+#define DD_BATCH 2048                      // most keys of a batch (256 points x 8, 64 cells x 27 = 1728, 256 cells x 8, 2048 keys)
+#define DD_FLUSH 1024                      // a batch is inserted only into a set with at most this many occupied slots
+// the probe loop ends at an EMPTY slot: the set is never full -- at most 3/4 of it is ever occupied
+static_assert(DD_FLUSH + DD_BATCH <= DD_SLOTS * 3 / 4 && (DD_SLOTS & (DD_SLOTS - 1)) == 0, "a batch must fit the set with room to spare");
 template <int SRC>   // 0: points (k_splat_keys)   1: cells (k_cell_footprint_keys)
 __global__ void __launch_bounds__(256) k_footprint_dedup(const float* __restrict__ xyz, const int64_t* __restrict__ cell_keys, int64_t n, float inv_w0,
-                                                         int level, int mode, int epb, int64_t* __restrict__ out,
+                                                         int level, int mode, int epb, int bpw, int64_t* __restrict__ out,
                                                          unsigned long long* __restrict__ counter) {
     __shared__ unsigned long long tab[DD_SLOTS];
     __shared__ int wsum[4];
     __shared__ unsigned long long gbase;
+    __shared__ int occupied;                                         // slots of tab that hold a key (from the EMPTY results of the atomicCAS)
     const unsigned long long EMPTY = ~0ull;
     for (int t = threadIdx.x; t < DD_SLOTS; t += 256) tab[t] = EMPTY;
+    if (threadIdx.x == 0) occupied = 0;
     __syncthreads();
     const int per = mode == 1 ? 27 : mode == 3 ? 1 : 8;
-    const int64_t e0 = (int64_t)blockIdx.x * epb;
-    const int ne = (int)(n - e0 < epb ? n - e0 : epb);
-    for (int t = threadIdx.x; t < ne * per; t += 256) {
-        const int e = t / per, sl = t - e * per;
-        const int64_t i = e0 + e;
-        int x, y, z, bias;
-        if (SRC == 0) {
-            float p;
-            const int hx = half_index(xyz[i * 3 + 0], inv_w0, p) >> level, hy = half_index(xyz[i * 3 + 1], inv_w0, p) >> level,
-                      hz = half_index(xyz[i * 3 + 2], inv_w0, p) >> level;
-            bias = NKSR_BIAS0 >> level;
-            if (mode == 0) { x = ((hx - 1) >> 1) + (sl >> 2); y = ((hy - 1) >> 1) + ((sl >> 1) & 1); z = ((hz - 1) >> 1) + (sl & 1); }
-            else { x = (hx >> 1) + sl / 9 - 1; y = (hy >> 1) + (sl / 3) % 3 - 1; z = (hz >> 1) + sl % 3 - 1; }
-        } else {
-            if (mode == 3) { x = y = z = bias = 0; }                                                    // the keys themselves
-            else morton_decode_biased(cell_keys[i], NKSR_BIAS0 >> level, x, y, z);
-            if (mode == 3) {}
-            else if (mode == 2) { bias = NKSR_BIAS0; x += sl >> 2; y += (sl >> 1) & 1; z += sl & 1; }       // lattice corners of a dual cell
-            else if (mode == 0) { bias = NKSR_BIAS0 >> (level + 1); x = ((x - 1) >> 1) + (sl >> 2); y = ((y - 1) >> 1) + ((sl >> 1) & 1); z = ((z - 1) >> 1) + (sl & 1); }
-            else { bias = NKSR_BIAS0 >> level; x += sl / 9 - 1; y += (sl / 3) % 3 - 1; z += sl % 3 - 1; }
-        }
-        const unsigned long long key = (SRC == 1 && mode == 3) ? (unsigned long long)cell_keys[e0 + t] : (unsigned long long)morton_biased(x, y, z, bias);
-        unsigned h = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 52);
-        for (;;) {
-            const unsigned long long prev = atomicCAS(&tab[h], EMPTY, key);
-            if (prev == EMPTY || prev == key) break;
-            h = (h + 1) & (DD_SLOTS - 1);
-        }
-    }
-    __syncthreads();
-    // ordered emission: thread t owns slots [16 t, 16 t + 16)
-    int cnt = 0;
-#pragma unroll
-    for (int q = 0; q < DD_SLOTS / 256; ++q) cnt += tab[threadIdx.x * (DD_SLOTS / 256) + q] != EMPTY;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = cnt;
+    const int64_t r0 = (int64_t)blockIdx.x * bpw * epb;              // the workgroup's range: elements [r0, r1)
+    const int64_t r1 = n - r0 < (int64_t)bpw * epb ? n : r0 + (int64_t)bpw * epb;
+    for (int64_t e0 = r0; e0 < r1; e0 += epb) {
+        const int ne = (int)(r1 - e0 < epb ? r1 - e0 : epb);
+        int fresh = 0;                                               // keys this wavefront put into EMPTY slots (uniform)
+        for (int t = threadIdx.x; t < ne * per; t += 256) {
+            const int e = t / per, sl = t - e * per;
+            const int64_t i = e0 + e;
+            int x, y, z, bias;
+            if (SRC == 0) {
+                float p;
+                const int hx = half_index(xyz[i * 3 + 0], inv_w0, p) >> level, hy = half_index(xyz[i * 3 + 1], inv_w0, p) >> level,
+                          hz = half_index(xyz[i * 3 + 2], inv_w0, p) >> level;
+                bias = NKSR_BIAS0 >> level;
+                if (mode == 0) { x = ((hx - 1) >> 1) + (sl >> 2); y = ((hy - 1) >> 1) + ((sl >> 1) & 1); z = ((hz - 1) >> 1) + (sl & 1); }
+                else { x = (hx >> 1) + sl / 9 - 1; y = (hy >> 1) + (sl / 3) % 3 - 1; z = (hz >> 1) + sl % 3 - 1; }
+            } else {
+                if (mode == 3) { x = y = z = bias = 0; }                                                    // the keys themselves
+                else morton_decode_biased(cell_keys[i], NKSR_BIAS0 >> level, x, y, z);
+                if (mode == 3) {}
+                else if (mode == 2) { bias = NKSR_BIAS0; x += sl >> 2; y += (sl >> 1) & 1; z += sl & 1; }       // lattice corners of a dual cell
+                else if (mode == 0) { bias = NKSR_BIAS0 >> (level + 1); x = ((x - 1) >> 1) + (sl >> 2); y = ((y - 1) >> 1) + ((sl >> 1) & 1); z = ((z - 1) >> 1) + (sl & 1); }
+                else { bias = NKSR_BIAS0 >> level; x += sl / 9 - 1; y += (sl / 3) % 3 - 1; z += sl % 3 - 1; }
+            }
+            const unsigned long long key = (SRC == 1 && mode == 3) ? (unsigned long long)cell_keys[e0 + t] : (unsigned long long)morton_biased(x, y, z, bias);
+            unsigned h = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 52);
+            bool took = false;
+            for (;;) {
+                const unsigned long long prev = atomicCAS(&tab[h], EMPTY, key);
+                took = prev == EMPTY;
+                if (took || prev == key) break;
+                h = (h + 1) & (DD_SLOTS - 1);
+            }
+            fresh += __popcll(__ballot(took));
+        }
+        if (lane == 0 && fresh) atomicAdd(&occupied, fresh);
+        __syncthreads();
+        const int occ = occupied;                                    // uniform: every thread reads it between the two barriers
+        __syncthreads();                                             // (the next batch adds to it again)
+        if (e0 + epb < r1 && occ <= DD_FLUSH) continue;               // the next batch (at most DD_BATCH keys) still fits
+        // ordered emission: thread t owns slots [16 t, 16 t + 16), and leaves them EMPTY for the next batch
+        unsigned long long mine[DD_SLOTS / 256];
+        int cnt = 0;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) gbase = atomicAdd(counter, (unsigned long long)(wsum[0] + wsum[1] + wsum[2] + wsum[3]));
-    __syncthreads();
-    int64_t pos = (int64_t)gbase + incl - cnt;
-    for (int w = 0; w < wave; ++w) pos += wsum[w];
+        for (int q = 0; q < DD_SLOTS / 256; ++q) {
+            mine[q] = tab[threadIdx.x * (DD_SLOTS / 256) + q];
+            cnt += mine[q] != EMPTY;
+            tab[threadIdx.x * (DD_SLOTS / 256) + q] = EMPTY;
+        }
+        int incl = cnt;
 #pragma unroll
-    for (int q = 0; q < DD_SLOTS / 256; ++q) {
-        const unsigned long long k = tab[threadIdx.x * (DD_SLOTS / 256) + q];
-        if (k != EMPTY) out[pos++] = (int64_t)k;
+        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        if (threadIdx.x == 0) { gbase = atomicAdd(counter, (unsigned long long)(wsum[0] + wsum[1] + wsum[2] + wsum[3])); occupied = 0; }
+        __syncthreads();
+        int64_t pos = (int64_t)gbase + incl - cnt;
+        for (int w = 0; w < wave; ++w) pos += wsum[w];
+#pragma unroll
+        for (int q = 0; q < DD_SLOTS / 256; ++q)
+            if (mine[q] != EMPTY) out[pos++] = (int64_t)mine[q];
     }
 }
 
-// Distinct-per-workgroup footprint keys of points (xyz != NULL: nksr_splat_keys) or of cells (cell_keys != NULL:
+#define DD_TARGET_WGS 2048
+#define DD_BPW_MIN 4
+#define DD_BPW_MAX 16
+// Distinct-per-workgroup-range footprint keys of points (xyz != NULL: nksr_splat_keys) or of cells (cell_keys != NULL:
 // nksr_cell_footprint_keys; mode 2: the 8 lattice corners of dual-grid cells, nksr_cell_corner_keys; mode 3: cell_keys is the
 // stream itself, any non-negative keys).  keys_out needs room for every key (n * 8 or n * 27); *count_out = number written.
 extern "C" int nksr_footprint_keys_dedup(const float* xyz, const int64_t* cell_keys, int64_t n, float inv_w0, int level, int mode,
@@ -481,10 +511,17 @@ extern "C" int nksr_footprint_keys_dedup(const float* xyz, const int64_t* cell_k
     hipStream_t st = (hipStream_t)stream;
     NKSR_CHECK_HIP(hipMemsetAsync(count_out, 0, sizeof(int64_t), st));
     if (n <= 0) return NKSR_OK;
-    const int epb = mode == 1 ? 64 : mode == 3 ? 2048 : 256;       // <= 2048 / 1728 keys per 4096-slot set
-    const dim3 grid((unsigned)((n + epb - 1) / epb));
-    if (xyz) hipLaunchKernelGGL(k_footprint_dedup<0>, grid, dim3(256), 0, st, xyz, cell_keys, n, inv_w0, level, mode, epb, keys_out, (unsigned long long*)count_out);
-    else hipLaunchKernelGGL(k_footprint_dedup<1>, grid, dim3(256), 0, st, xyz, cell_keys, n, inv_w0, level, mode, epb, keys_out, (unsigned long long*)count_out);
+    const int epb = mode == 1 ? 64 : mode == 3 ? DD_BATCH : 256;   // elements of a batch: <= DD_BATCH keys (2048 / 1728)
+    // Batches per workgroup.  The fewer workgroups, the fewer tickets and the more repeats one set sees; but the kernel needs the
+    // whole GPU: 8 workgroups per CU (256 CUs; five 32 KB sets fit a CU at a time) keep the last round of workgroups short.  So a
+    // range is  batches / 2048, at least DD_BPW_MIN (a 2^19-key stream still spreads over 64 workgroups: its 4 MB take microseconds
+    // either way) and at most DD_BPW_MAX (a 10 M-point stream: 39 k batches -> 2442 workgroups).
+    const int64_t nbatch = (n + epb - 1) / epb;
+    const int64_t want = nbatch / DD_TARGET_WGS;
+    const int bpw = (int)(want < DD_BPW_MIN ? DD_BPW_MIN : want > DD_BPW_MAX ? DD_BPW_MAX : want);
+    const dim3 grid((unsigned)((nbatch + bpw - 1) / bpw));
+    if (xyz) hipLaunchKernelGGL(k_footprint_dedup<0>, grid, dim3(256), 0, st, xyz, cell_keys, n, inv_w0, level, mode, epb, bpw, keys_out, (unsigned long long*)count_out);
+    else hipLaunchKernelGGL(k_footprint_dedup<1>, grid, dim3(256), 0, st, xyz, cell_keys, n, inv_w0, level, mode, epb, bpw, keys_out, (unsigned long long*)count_out);
     NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }

@@ -116,7 +116,8 @@ def fill_rows(fld, sets, first_rows, R):
 def operator_tables(fld, R, item_seg, segments):
     """Work items = runs of 32 rows, eight of them a workgroup of the sweep; a cell whose rows lie inside one workgroup is finished
     there, a cell that reaches into k > 1 workgroups owns k partial blocks (the coarse cells: ~1 % of all).  Returns the
-    nksr_fused_op_t, span (first / last row of every cell, first workgroup), nblocks, n_multi, nnz_counter and the buffers to keep."""
+    nksr_fused_op_t, span (first / last row of every cell, first workgroup), nblocks, n_multi, nnz_counter (one int64: the stored
+    entries once nksr_fused_rhs_diag has run), nnz_scratch (the sweep's per-workgroup counts behind it) and the buffers to keep."""
     dev, L, M, rows_total = fld.device, fld.svh.depth, fld.svh.num_unknowns, R['rows_total']
     span = torch.empty((3, M), dtype=torch.int32, device=dev)
     counts = torch.empty(M + 1, dtype=torch.int32, device=dev)
@@ -140,13 +141,17 @@ def operator_tables(fld, R, item_seg, segments):
     op.offsets, op.multi, op.workspace, op.cell_sums = ptr(offsets), (ptr(multi) if multi.numel() else None), ptr(ws), ptr(cell_sums)
     # SURVEY.md section 8d counts the operator's bytes per STORED entry; the dense-slot rows hold structural zeros (absent
     # neighbours, B-spline support ends): the set-up pass counts the non-zero slots on its way (read back on demand)
-    nnz_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-    op.nnz_counter = ptr(nnz_counter)
-    keep = [nbr32, nbrT, item_begin, offsets, multi, ws, cell_sums, nnz_counter]
+    # (word 0: the total; behind it the sweep's scratch, one count per workgroup, no initial value -- the sweep shares no word)
+    nnz_words = torch.empty(int(_lib.lib.nksr_fused_count_words(rows_total)), dtype=torch.int64, device=dev)
+    nnz_counter, nnz_scratch = nnz_words[:1], nnz_words[1:]
+    nnz_counter.zero_()
+    op.nnz_counter = ptr(nnz_words)
+    keep = [nbr32, nbrT, item_begin, offsets, multi, ws, cell_sums, nnz_words]
     if item_seg is not None:
         op.item_seg, op.unknown_seg = ptr(item_seg), ptr(segments.unknown_seg)
         keep += [item_seg, segments.unknown_seg]
-    return {'op': op, 'span': span, 'nblocks': nblocks, 'n_multi': int(multi.numel()), 'nnz_counter': nnz_counter, 'keep': keep}
+    return {'op': op, 'span': span, 'nblocks': nblocks, 'n_multi': int(multi.numel()), 'nnz_counter': nnz_counter, 'nnz_scratch': nnz_scratch,
+            'keep': keep}
 
 
 def fused_operator(fld, pos_xyz, normal_xyz, normal_value, pos_weight, normal_weight, pos_sorted_keys=None, normal_sorted_keys=None,

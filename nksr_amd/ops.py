@@ -115,7 +115,9 @@ def sort_unique(keys, maybe_sorted=False, level=None):
 
 
 def dedup_keys(keys):
-    """A shorter stream with the same key set: repeats within runs of 2048 consecutive keys dropped (mode 3)."""
+    """A shorter stream with the same key set (mode 3): a workgroup takes a contiguous range of the stream (4 to 16 batches of 2048
+    keys) through one LDS set, which it emits when it fills up and at the end of the range -- repeats are dropped within a
+    workgroup's range (as far as the set lasts), not within 2048 keys.  The order of the result is free."""
     n = keys.numel()
     raw = torch.empty(n, dtype=torch.int64, device=keys.device)
     cnt = torch.empty(1, dtype=torch.int64, device=keys.device)

@@ -153,7 +153,9 @@ class SparseFeatureHierarchy:
 
     def _dedup(self, xyz, cells, n, level, mode, raw):
         """Large key streams: duplicates of neighbouring (Morton-ordered) elements are dropped in LDS before the sort
-        (nksr_footprint_keys_dedup): the level-0 streams of a 1 M-point cloud shrink from 8-11 M keys to 1-2 M."""
+        (nksr_footprint_keys_dedup): the level-0 streams of a 1 M-point cloud shrink from 8-11 M keys to 1-2 M.  Repeats are
+        dropped within a workgroup's RANGE of elements (4 to 16 batches of 256 points / 64 or 256 cells, one LDS set that is
+        emitted when it fills up and at the end of the range), not within one batch; the order of the result is free."""
         cnt = torch.empty(1, dtype=torch.int64, device=self.device)
         call('nksr_footprint_keys_dedup', ptr(xyz) if xyz is not None else None, ptr(cells) if cells is not None else None, n,
              self.inv_w0, level, mode, ptr(raw), ptr(cnt), stream())
