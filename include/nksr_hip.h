@@ -260,6 +260,31 @@ int nksr_assemble(const nksr_hier_t* h, const nksr_siteset_t* sets, int nsets, f
 int nksr_place_mirrors(const uint64_t* keys_sorted, const float* vals_sorted, int64_t n, int col_bits,
                        const int32_t* rowptr, const int32_t* mirptr, int col_format, int32_t* cols_out, float* vals_out,
                        void* stream);
+/* The format-1 block of the coarse-level preconditioner (nksr_coarse_precond_t below) WITHOUT the fp32 CSR: word for word what
+ * nksr_assemble (col_format 2) + nksr_place_mirrors + nksr_coarse_pack_count + nksr_coarse_pack give.  Four calls, two scans and one
+ * keys-only sort between them (nksr_amd/fields/assembly.py: assemble_packed):
+ *  1. nksr_assemble_packed: Gram blocks, then diag_out (every row's diagonal, ahead of the fill and bitwise the fill's), then the row
+ *     fill with the drop test inside.  own_off = exclusive scan of (samelow + rowcount), mir_off = exclusive scan of crosscount,
+ *     new_of_old = segment-major renumbering, local_col[r] = new_of_old[r] - seg_base[segment of r].  Kept own entries leave as final
+ *     packed words inside [own_off[r], own_off[r + 1]) of own_out (lower run from its start, upper run from + samelow[r]); the mirror of
+ *     every kept cross-level entry as  destination row (new) << 32 | half << 16 | local column of the source  inside
+ *     [mir_off[r], mir_off[r + 1]) of mir_out; kept_out [3][n + 1] = kept lower / upper / mirror entries per row.
+ *  2. nksr_packed_mirrors_compact: the kept mirror words as a dense list in ascending source row (kept_off = exclusive scan of
+ *     kept_out[2]); it is then sorted stably on bits [32, 32 + bits(n)) (nksr_sort_keys_u64).
+ *  3. nksr_packed_row_lengths: runs_out [2][n] = begin / end of every new row's run in the sorted list, lens_out [n] = run + kept own
+ *     entries of new row i; packed_rowptr = exclusive scan of lens_out.
+ *  4. nksr_packed_rows: row i = [mirrors][same-level lower][own upper], and dis_out (new order). */
+int nksr_assemble_packed(const nksr_hier_t* h, const nksr_siteset_t* sets, int nsets, float reg, void* workspace,
+                         const int32_t* samelow, const int32_t* mir_off, const int32_t* own_off, const int32_t* new_of_old,
+                         const int32_t* local_col, float drop_tol, float* diag_out, uint32_t* own_out, uint64_t* mir_out,
+                         int32_t* kept_out, void* split_scratch, size_t split_scratch_bytes, void* stream);
+int nksr_packed_mirrors_compact(int32_t n, const uint64_t* mir_staged, const int32_t* mir_off, const int32_t* kept_mir,
+                                const int32_t* kept_off, uint64_t* mir_dense, void* stream);
+int nksr_packed_row_lengths(int32_t n, const uint64_t* mir_sorted, int64_t n_mir, const int32_t* kept, const int32_t* old_of_new,
+                            int32_t* runs_out, int32_t* lens_out, void* stream);
+int nksr_packed_rows(int32_t n, const uint64_t* mir_sorted, const int32_t* runs, const uint32_t* own, const int32_t* own_off,
+                     const int32_t* samelow, const int32_t* kept, const int32_t* old_of_new, const int32_t* packed_rowptr,
+                     const float* diag, uint32_t* packed_out, float* dis_out, void* stream);
 
 /* ---- PCG (the CG SpMV is the roofline kernel) -------------------- */
 /* nnz-chunked streaming CSR SpMV (csrc/pcg.hip).  cols/vals live in a tile-interleaved physical layout

@@ -20,8 +20,13 @@
 //  4. a STABLE radix sort of that list on the destination-row bits (3 passes over HALF of the
 //     entries) orders every row's mirrors by ascending source row; k_place_mirrors drops them into
 //     the CSR.  Deterministic and exactly symmetric, no float atomics, no full COO.
+//  The coarse-level block of the PCG's preconditioner, when it is stored packed (csrc/pcg.hip, format 1), skips the CSR: steps 3 and 4
+//  become  3'. k_row_diag (every diagonal, ahead of the fill) + the fill with the drop test inside (kept entries leave as packed words),
+//  4'. the kept mirror words alone compacted, sorted keys-only, and one kernel that writes the packed rows -- "the packed coarse block
+//  straight from the slot frame" below, nksr_assemble_packed in include/nksr_hip.h.
 #include "common.h"
 #include <stdlib.h>
+#include <hip/hip_fp16.h>
 
 #define ASM_WAVES 1
 
@@ -66,6 +71,8 @@ __device__ __forceinline__ int64_t csr_phys(int64_t k, int fmt) {
 // A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]).  Column T carries the right-hand side
 // (27 m is never a multiple of 32, so a spare column always exists).  The set weight scales the A
 // operand (the host passes rows pre-multiplied by sqrt(w) and weight 1, see below).  Accumulator register r of lane l is D[row = (r & 3) + 8 (r >> 2) + 4 (l >> 5)][col = l & 31].
+// That column map is the site sets' (asm_accumulate_rows, k_cell_blocks).  The operator's row list (asm_accumulate_lm) lets tile n hold
+// LEVEL d + n instead, so that a half-wave load is one 108-byte row of one level's array: see asm_lm_pointers.
 typedef float asm_f32x16 __attribute__((ext_vector_type(16)));
 
 // entry `col` (slot col % 27 of level d + col / 27) of site row q: site-major rows [n ncomp, L, 27], or -- level_stride > 0 -- the
@@ -79,8 +86,10 @@ __device__ __forceinline__ float asm_row_value(const nksr_siteset_t& S, int64_t 
 }
 
 // writes the accumulated tile(s) of cell c: block rows whose voxel exists, the right-hand-side column, the site count
+// ``by_level``: the accumulator tiles came from asm_accumulate_lm, whose tile n holds level d + n (slot j in lane j < 27, the
+// right-hand side in lane 27 of tile 0) -- not columns 32 n .. 32 n + 31 of the concatenated levels
 template <int NT>
-__device__ __forceinline__ void cell_blocks_finalize(const AsmArgs& A, int d, int c, int lane, asm_f32x16 (&acc)[NT], int total) {
+__device__ __forceinline__ void cell_blocks_finalize(const AsmArgs& A, int d, int c, int lane, asm_f32x16 (&acc)[NT], int total, bool by_level = false) {
     const nksr_level_t& lv = A.hier.lv[d];
     const int T = (A.hier.depth - d) * 27;
     const int j = lane & 31, half = lane >> 5;
@@ -99,8 +108,13 @@ __device__ __forceinline__ void cell_blocks_finalize(const AsmArgs& A, int d, in
         for (int r = 0; r < 16; ++r) {
             const int s = (r & 3) + 8 * (r >> 2) + 4 * half;
             if (s < 27 && ((need >> s) & 1ull)) {
-                if (col < T) out[s * T + col] = acc[n][r];
-                else if (col == T) bv[s] = acc[n][r];
+                if (by_level) {
+                    if (j < 27) { if (27 * n < T) out[s * T + 27 * n + j] = acc[n][r]; }
+                    else if (n == 0 && j == 27) bv[s] = acc[n][r];
+                } else {
+                    if (col < T) out[s * T + col] = acc[n][r];
+                    else if (col == T) bv[s] = acc[n][r];
+                }
             }
         }
     }
@@ -169,22 +183,24 @@ __device__ __forceinline__ void asm_lm_mfma(const AsmLanePtr<NT>& P, int r0, int
         for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v[n], acc[n], 0, 0, 0);
     }
 }
-// lane pointers of level d's column tiles (they do not depend on the cell)
+// lane pointers of level d's column tiles (they do not depend on the cell).  Tile n holds LEVEL d + n: slot j in lane j < 27 (NT =
+// ceil((T + 1) / 32) tiles are as many as there are levels, because 27 <= 32), the right-hand side in lane 27 of tile 0; the lanes
+// left over are clamped onto slot 26 of their tile's row and masked.  A half-wave load is then ONE 108-byte row of one level's array
+// (with columns 32 n + j it straddled two levels' arrays, which lie level_stride rows apart, and the idle lanes of the last tile read
+// a third place: 4-6 cache lines per load instruction for two rows where 2-4 do).  Every block element is still the sum of the same
+// products over the rows in the same order -- only the (tile, lane) that holds it moved, cell_blocks_finalize(by_level) knows where.
 template <int NT>
 __device__ __forceinline__ void asm_lm_pointers(const AsmArgs& A, int d, int lane, AsmLanePtr<NT>& P) {
     const nksr_siteset_t& S = A.sets[0];
-    const int L = A.hier.depth;
-    const int T = (L - d) * 27;
+    const int levels = A.hier.depth - d;
     const int j = lane & 31;
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
-        const int col = 32 * n + j;
-        const int dd = col / 27, sl = col - dd * 27;
-        P.on[n] = col < T || (col == T && S.target);
-        P.mul[n] = (col == T && S.target) ? 1 : 27;
-        // (columns past T are never used but their loads are unconditional: they read level d -- the array may START at level
-        // S.level_base, KernelField.assemble, and the launch's levels are >= it)
-        P.p[n] = (col == T && S.target) ? S.target : S.val + (col < T ? (int64_t)(d + dd - S.level_base) * S.level_stride * 27 + sl : (int64_t)(d - S.level_base) * S.level_stride * 27);
+        const bool rhs = n == 0 && j == 27 && S.target;
+        const int dd = n < levels ? n : 0;      // (a tile past the last level is never used but its loads are unconditional: it reads level d)
+        P.on[n] = (n < levels && j < 27) || rhs;
+        P.mul[n] = rhs ? 1 : 27;
+        P.p[n] = rhs ? S.target : S.val + (int64_t)(d + dd - S.level_base) * S.level_stride * 27 + (j < 27 ? j : 26);
     }
 }
 template <int NT>
@@ -293,7 +309,7 @@ __global__ void __launch_bounds__(ASM_WAVES * 64) k_cell_blocks_reduce(AsmArgs A
     }
     int total = 0;
     for (int si = 0; si < A.nsets; ++si) total += A.sets[si].end[d][c] - A.sets[si].start[d][c];
-    cell_blocks_finalize<NT>(A, d, c, lane, acc, total);
+    cell_blocks_finalize<NT>(A, d, c, lane, acc, total, asm_is_row_list(A));
 }
 
 // the same sum, one wavefront per cell: part after part into a fresh accumulator, added to the total in order
@@ -327,7 +343,7 @@ __global__ void __launch_bounds__(ASM_WAVES * 64) k_cell_blocks_seq(AsmArgs A, i
     }
     int total = 0;
     for (int si = 0; si < A.nsets; ++si) total += A.sets[si].end[d][c] - A.sets[si].start[d][c];
-    cell_blocks_finalize<NT>(A, d, c, lane, tot, total);
+    cell_blocks_finalize<NT>(A, d, c, lane, tot, total, asm_is_row_list(A));
 }
 
 // LM: the site sets hold LEVEL-MAJOR rows (nksr_siteset_t.level_stride > 0)
@@ -350,7 +366,7 @@ __global__ void __launch_bounds__(ASM_WAVES * 64) k_cell_blocks(AsmArgs A, int d
         const int k0 = A.sets[0].start[d][c], k1 = A.sets[0].end[d][c];
         total = k1 > k0 ? k1 - k0 : 0;
         asm_accumulate_lm<NT>(A, d, k0, k1, lane, acc);
-        cell_blocks_finalize<NT>(A, d, c, lane, acc, total);
+        cell_blocks_finalize<NT>(A, d, c, lane, acc, total, true);
         return;
     }
     for (int si = 0; si < A.nsets; ++si) {
@@ -553,15 +569,65 @@ __device__ __forceinline__ void load_cols(const float* __restrict__ row, int lan
     }
 }
 
-// ---- phase 2b: one wavefront per row: gather block rows into the slot frame, emit COO ----------------
-template <int NQ>
+// ---- the packed coarse block straight from the slot frame (nksr_assemble_packed) ---------------------------------------------------
+// The preconditioner's block is stored Jacobi-scaled in half precision with the entries below `drop` of the unit diagonal left out
+// (csrc/pcg.hip, format 1): a row is assembled with ~250 entries and keeps ~37.  The drop test of entry (i, j) needs nothing the fill
+// does not hold except the diagonal of row j, and that is ONE element of each of the 27 neighbour cells' blocks: k_row_diag forms all
+// diagonals ahead of the fill (same terms, same order, same bits), and the fill (PACK) emits only what survives --
+//   own entries (same-level lower, own upper) as final packed words  half << 16 | column local to the segment,  compacted inside the
+//     row's structural range [own_off[row], own_off[row + 1]): the lower run from its start, the upper run from + samelow[row];
+//   the mirror of a kept cross-level entry as one 64-bit word  destination row (new order) << 32 | half << 16 | local column of the
+//     SOURCE row,  compacted inside [mir_off[row], mir_off[row + 1]);
+//   kept[0 / 1 / 2][row] = kept lower / upper / mirror entries.
+// The kept mirror words are then compacted to a dense list (ascending source row), sorted stably on the destination bits alone
+// (keys only, a seventh of the entries at 8 instead of 12 bytes), and k_pk_rows writes every row  [mirrors][lower][upper]  in the
+// new order: word for word what nksr_coarse_pack makes of the fp32 CSR, which is never written.
+// cc_scaled / cc_keep: the drop rule of csrc/pcg.hip (k_cc_pack), restated -- tests/test_gpu_coarse_direct.py compares the two paths
+// word for word.
+__device__ __forceinline__ __half cc_scaled(float v, float di, float dj) { return __float2half_rn(v * (di * dj)); }
+__device__ __forceinline__ bool cc_keep(__half hv, float drop) { return fabsf(__half2float(hv)) >= drop; }
+
+struct AsmPackOut {
+    const float* diag;          // [M] from k_row_diag
+    const int32_t* new_of_old;  // [M] segment-major renumbering
+    const int32_t* local;       // [M] new_of_old[row] - seg_base[segment of row]
+    const int32_t* own_off;     // [M + 1] exclusive scan of samelow + rowcount
+    uint32_t* own;              // kept own words
+    uint64_t* mir;              // kept mirror words
+    int32_t* kept;              // [3][M + 1]
+    float drop;
+};
+
+// diag[row] = acc[62] + reg of the fill: the block element (row 26 - s, column 26 - s) of every neighbour cell s that holds sites, added
+// in ascending s from 0.f -- the order of the fill's batches.  32 lanes per row.
+__global__ void __launch_bounds__(256) k_row_diag(AsmArgs A, float* __restrict__ diag) {
+    const int row = (blockIdx.x * 256 + threadIdx.x) >> 5, l = threadIdx.x & 31;
+    if (row >= A.M) return;
+    const nksr_hier_t& h = A.hier;
+    const int d = row_level(h, row);
+    const nksr_level_t& lv = h.lv[d];
+    const int i = row - lv.offset;
+    const int T = (h.depth - d) * 27;
+    const int c = (l < 27) ? lv.nbr[(int64_t)i * 27 + l] : -1;
+    const int on = (c >= 0 && A.nsites[d][c] > 0) ? 1 : 0;
+    const float x = on ? A.blocks[d][((int64_t)c * 27 + (26 - l)) * T + (26 - l)] : 0.f;
+    float s = 0.f;
+    for (int sp = 0; sp < 27; ++sp) {
+        const float v = __shfl(x, sp, 32);
+        if (__shfl(on, sp, 32)) s += v;
+    }
+    if (l == 0) diag[row] = s + A.reg;
+}
+
+// ---- phase 2b: one wavefront per row: gather block rows into the slot frame, emit COO (or, PACK, the kept packed words) ----------
+template <int NQ, bool PACK>
 __global__ void __launch_bounds__(ASM_WAVES * 64) k_row_fill(AsmArgs A, const int32_t* __restrict__ rowptr,
                                                              const int32_t* __restrict__ indeg, const int32_t* __restrict__ samelow,
                                                              const int32_t* __restrict__ mir_off,
                                                              int32_t* __restrict__ cols_out, float* __restrict__ vals_out,
                                                              float* __restrict__ diag_out, uint64_t* __restrict__ mir_keys,
                                                              float* __restrict__ mir_vals,
-                                                             float* __restrict__ b_out, int row_begin, int row_end) {
+                                                             float* __restrict__ b_out, int row_begin, int row_end, AsmPackOut K) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int row = row_begin + blockIdx.x * ASM_WAVES + wave;
@@ -581,10 +647,12 @@ __global__ void __launch_bounds__(ASM_WAVES * 64) k_row_fill(AsmArgs A, const in
     const int cme = (lane < 27) ? lv.nbr[(int64_t)i * 27 + lane] : -1;
     const int nse = (cme >= 0) ? A.nsites[d][cme] : 0;
     unsigned long long act = __ballot(nse > 0);
-    float bl = (nse > 0) ? A.bvec[d][(int64_t)cme * 27 + (26 - lane)] : 0.f;
+    if (!PACK) {                       // (the preconditioner's block has no right-hand side)
+        float bl = (nse > 0) ? A.bvec[d][(int64_t)cme * 27 + (26 - lane)] : 0.f;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bl += __shfl_xor(bl, o);
-    if (lane == 0) b_out[row] = bl;
+        for (int o = 32; o > 0; o >>= 1) bl += __shfl_xor(bl, o);
+        if (lane == 0) b_out[row] = bl;
+    }
 
     // per-lane entry decomposition (independent of the neighbour cell)
     int edd[NQ], esx[NQ], esy[NQ], esz[NQ];
@@ -641,6 +709,46 @@ __global__ void __launch_bounds__(ASM_WAVES * 64) k_row_fill(AsmArgs A, const in
 
     // emission: structure comes from the count pass (no hashing here)
     const int32_t* cm = A.colmap[d] + (int64_t)i * nslots;
+    if (PACK) {
+        const float di = 1.f / sqrtf(K.diag[row]);
+        const int local = K.local[row];
+        const int base = K.new_of_old[row] - local;               // first new row of this row's segment
+        int lpos = K.own_off[row];
+        int opos = lpos + samelow[row];
+        int mpos = mir_off[row];
+        const int l0 = lpos, o0 = opos, m0 = mpos;
+        for (int t0 = 0; t0 < nslots; t0 += 64) {
+            const int t = t0 + lane;
+            const int cv = (t < nslots) ? cm[t] : -1;
+            const bool up = cv >= 0, low = cv <= -2;
+            bool keep = false;
+            uint32_t hbits = 0u;
+            int ncol = 0;
+            if (up | low) {
+                const int col = up ? cv : -2 - cv;
+                const __half hv = cc_scaled(acc[t], di, 1.f / sqrtf(K.diag[col]));
+                keep = cc_keep(hv, K.drop);
+                hbits = (uint32_t)__half_as_ushort(hv) << 16;
+                ncol = K.new_of_old[col];
+            }
+            const bool ku = keep && up, kl = keep && low, km = ku && t >= 125;
+            const unsigned long long mu = __ballot(ku), ml = __ballot(kl), mm = __ballot(km);
+            const unsigned long long below = (1ull << lane) - 1ull;
+            if (keep) {
+                K.own[ku ? opos + __popcll(mu & below) : lpos + __popcll(ml & below)] = hbits | (uint32_t)(ncol - base);
+                if (km) K.mir[mpos + __popcll(mm & below)] = ((uint64_t)(uint32_t)ncol << 32) | (uint64_t)(hbits | ((uint32_t)local & 0xFFFFu));
+            }
+            opos += __popcll(mu);
+            lpos += __popcll(ml);
+            mpos += __popcll(mm);
+        }
+        if (lane == 0) {
+            K.kept[row] = lpos - l0;
+            K.kept[(int64_t)(A.M + 1) + row] = opos - o0;
+            K.kept[2 * (int64_t)(A.M + 1) + row] = mpos - m0;
+        }
+        return;
+    }
     // row = [cross-level mirrors (from finer rows)][same-level lower][own upper][diagonal].  Same-level lower and
     // own upper entries go straight to their final CSR slot; only the cross-level upper entries have a
     // mirrored copy, which goes to a list keyed by destination row, sorted afterwards
@@ -690,6 +798,55 @@ __global__ void k_place_mirrors(const uint64_t* __restrict__ keys, const float* 
     const int64_t ph = csr_phys((int64_t)rowptr[r] + (m - (int64_t)mirptr[r]), fmt);
     cols_out[ph] = src;
     vals_out[ph] = vals[m];
+}
+
+// kept mirror words of row r: [mir_off[r], + kept[r]) of the structural list -> [kept_off[r], ...) of the dense one.  16 lanes per row.
+__global__ void __launch_bounds__(256) k_pk_compact(int M, const uint64_t* __restrict__ staged, const int32_t* __restrict__ mir_off,
+                                                    const int32_t* __restrict__ kept, const int32_t* __restrict__ kept_off,
+                                                    uint64_t* __restrict__ dense) {
+    const int r = (blockIdx.x * 256 + threadIdx.x) >> 4, l = threadIdx.x & 15;
+    if (r >= M) return;
+    const int n = kept[r], src = mir_off[r], dst = kept_off[r];
+    for (int k = l; k < n; k += 16) dense[dst + k] = staged[src + k];
+}
+
+// run [runs[d], runs[n + d]) of destination row d in the sorted mirror words (both zero where a row has none: cleared by the caller)
+__global__ void __launch_bounds__(256) k_pk_runs(const uint64_t* __restrict__ sorted, int nk, int n, int32_t* __restrict__ runs) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= nk) return;
+    const int d = (int)(sorted[m] >> 32);
+    if (m == 0 || (int)(sorted[m - 1] >> 32) != d) runs[d] = m;
+    if (m == nk - 1 || (int)(sorted[m + 1] >> 32) != d) runs[n + d] = m + 1;
+}
+
+__global__ void __launch_bounds__(256) k_pk_lens(int n, const int32_t* __restrict__ runs, const int32_t* __restrict__ kept,
+                                                 const int32_t* __restrict__ old_of_new, int32_t* __restrict__ lens) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int o = old_of_new[i];
+    lens[i] = (runs[n + i] - runs[i]) + kept[o] + kept[(int64_t)(n + 1) + o];
+}
+
+// row i of the packed block (new order) = [kept mirrors, ascending source row][kept same-level lower][kept own upper] -- the order
+// k_cc_pack (csrc/pcg.hip) leaves of the CSR row -- and dis[i] = D^-1/2.  16 lanes per row.
+__global__ void __launch_bounds__(256) k_pk_rows(int n, const uint64_t* __restrict__ sorted, const int32_t* __restrict__ runs,
+                                                 const uint32_t* __restrict__ own, const int32_t* __restrict__ own_off,
+                                                 const int32_t* __restrict__ samelow, const int32_t* __restrict__ kept,
+                                                 const int32_t* __restrict__ old_of_new, const int32_t* __restrict__ prow,
+                                                 const float* __restrict__ diag, uint32_t* __restrict__ pk, float* __restrict__ dis) {
+    const int i = (blockIdx.x * 256 + threadIdx.x) >> 4, l = threadIdx.x & 15;
+    if (i >= n) return;
+    const int o = old_of_new[i];
+    int p = prow[i];
+    const int mb = runs[i], nm = runs[n + i] - mb;
+    for (int k = l; k < nm; k += 16) pk[p + k] = (uint32_t)sorted[mb + k];
+    p += nm;
+    const int lo = own_off[o], nl = kept[o], nu = kept[(int64_t)(n + 1) + o];
+    for (int k = l; k < nl; k += 16) pk[p + k] = own[lo + k];
+    p += nl;
+    const int up = lo + samelow[o];
+    for (int k = l; k < nu; k += 16) pk[p + k] = own[up + k];
+    if (l == 0) dis[i] = 1.f / sqrtf(diag[o]);
 }
 
 static int fill_args(AsmArgs& A, const nksr_hier_t* h, const nksr_siteset_t* sets, int nsets, float reg, int col_bits,
@@ -760,20 +917,10 @@ extern "C" int nksr_assemble_count(const nksr_hier_t* h, void* workspace, int32_
     return NKSR_OK;
 }
 
-extern "C" int nksr_assemble(const nksr_hier_t* h, const nksr_siteset_t* sets, int nsets, float reg, int col_bits,
-                             void* workspace, const int32_t* rowptr, const int32_t* indeg, const int32_t* samelow,
-                             const int32_t* mir_off, int col_format,
-                             int32_t* cols_out, float* vals_out, float* diag_out, uint64_t* mir_keys, float* mir_vals,
-                             float* b_out, void* split_scratch, size_t split_scratch_bytes, void* stream) {
-    AsmArgs A;
-    int rc = fill_args(A, h, sets, nsets, reg, col_bits, workspace);
-    if (rc) return rc;
-    if (col_format < 0 || col_format > 2) return nksr_set_error(NKSR_ERR_ARG, "col_format must be 0, 1 or 2");
-    A.col_format = col_format;
-    if (A.M <= 0) return NKSR_OK;
-    hipStream_t st = (hipStream_t)stream;
+// phase 1 of every level: the per-cell Gram blocks
+static int launch_cell_blocks(const AsmArgs& A, const nksr_hier_t* h, const nksr_siteset_t* sets, int nsets, void* split_scratch,
+                              size_t split_scratch_bytes, hipStream_t st) {
     const dim3 blk(ASM_WAVES * 64);
-    const size_t lds = (size_t)ASM_WAVES * NKSR_MAX_DEPTH * 125 * sizeof(float);
     int64_t total_rows = 0;
     bool lm = false;
     for (int si = 0; si < nsets; ++si) {
@@ -819,17 +966,105 @@ extern "C" int nksr_assemble(const nksr_hier_t* h, const nksr_siteset_t* sets, i
         }
         NKSR_CHECK_LAUNCH();
     }
+    return NKSR_OK;
+}
+
+// phase 2b of every level.  K == nullptr: the CSR; otherwise the kept packed words (k_row_fill<.., true>)
+static int launch_row_fill(const AsmArgs& A, const nksr_hier_t* h, const int32_t* rowptr, const int32_t* indeg, const int32_t* samelow,
+                           const int32_t* mir_off, int32_t* cols_out, float* vals_out, float* diag_out, uint64_t* mir_keys,
+                           float* mir_vals, float* b_out, const AsmPackOut* K, hipStream_t st) {
+    const dim3 blk(ASM_WAVES * 64);
+    const size_t lds = (size_t)ASM_WAVES * NKSR_MAX_DEPTH * 125 * sizeof(float);
+    AsmPackOut none;
+    memset(&none, 0, sizeof(none));
     for (int d = 0; d < h->depth; ++d) {
         const int n = h->lv[d].n;
         if (n <= 0) continue;
         const int T = (h->depth - d) * 27;
         const int r0 = h->lv[d].offset, r1 = r0 + n;
         const dim3 grid(nksr_blocks(n, ASM_WAVES));
-#define ROWFILL(NQ) hipLaunchKernelGGL((k_row_fill<NQ>), grid, blk, lds, st, A, rowptr, indeg, samelow, mir_off, cols_out, vals_out, diag_out, \
-                                       mir_keys, mir_vals, b_out, r0, r1)
+#define ROWFILL(NQ) do { if (K) hipLaunchKernelGGL((k_row_fill<NQ, true>), grid, blk, lds, st, A, rowptr, indeg, samelow, mir_off, cols_out, vals_out, \
+                                                   diag_out, mir_keys, mir_vals, b_out, r0, r1, *K); \
+                         else hipLaunchKernelGGL((k_row_fill<NQ, false>), grid, blk, lds, st, A, rowptr, indeg, samelow, mir_off, cols_out, vals_out, \
+                                                 diag_out, mir_keys, mir_vals, b_out, r0, r1, none); } while (0)
         if (T > 128) ROWFILL(3); else if (T > 64) ROWFILL(2); else ROWFILL(1);
         NKSR_CHECK_LAUNCH();
     }
+    return NKSR_OK;
+}
+
+extern "C" int nksr_assemble(const nksr_hier_t* h, const nksr_siteset_t* sets, int nsets, float reg, int col_bits,
+                             void* workspace, const int32_t* rowptr, const int32_t* indeg, const int32_t* samelow,
+                             const int32_t* mir_off, int col_format,
+                             int32_t* cols_out, float* vals_out, float* diag_out, uint64_t* mir_keys, float* mir_vals,
+                             float* b_out, void* split_scratch, size_t split_scratch_bytes, void* stream) {
+    AsmArgs A;
+    int rc = fill_args(A, h, sets, nsets, reg, col_bits, workspace);
+    if (rc) return rc;
+    if (col_format < 0 || col_format > 2) return nksr_set_error(NKSR_ERR_ARG, "col_format must be 0, 1 or 2");
+    A.col_format = col_format;
+    if (A.M <= 0) return NKSR_OK;
+    rc = launch_cell_blocks(A, h, sets, nsets, split_scratch, split_scratch_bytes, (hipStream_t)stream);
+    if (rc) return rc;
+    return launch_row_fill(A, h, rowptr, indeg, samelow, mir_off, cols_out, vals_out, diag_out, mir_keys, mir_vals, b_out, nullptr,
+                           (hipStream_t)stream);
+}
+
+extern "C" int nksr_assemble_packed(const nksr_hier_t* h, const nksr_siteset_t* sets, int nsets, float reg, void* workspace,
+                                    const int32_t* samelow, const int32_t* mir_off, const int32_t* own_off, const int32_t* new_of_old,
+                                    const int32_t* local_col, float drop_tol, float* diag_out, uint32_t* own_out, uint64_t* mir_out,
+                                    int32_t* kept_out, void* split_scratch, size_t split_scratch_bytes, void* stream) {
+    AsmArgs A;
+    int rc = fill_args(A, h, sets, nsets, reg, 32, workspace);
+    if (rc) return rc;
+    if (!samelow || !mir_off || !own_off || !new_of_old || !local_col || !diag_out || !own_out || !mir_out || !kept_out)
+        return nksr_set_error(NKSR_ERR_ARG, "NULL arrays");
+    if (!(drop_tol >= 0.f) || drop_tol >= 1.f) return nksr_set_error(NKSR_ERR_ARG, "drop_tol must be in [0, 1)");
+    A.col_format = 2;
+    if (A.M <= 0) return NKSR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    rc = launch_cell_blocks(A, h, sets, nsets, split_scratch, split_scratch_bytes, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_row_diag, dim3(nksr_blocks((int64_t)A.M * 32, 256)), dim3(256), 0, st, A, diag_out);
+    NKSR_CHECK_LAUNCH();
+    AsmPackOut K;
+    K.diag = diag_out; K.new_of_old = new_of_old; K.local = local_col; K.own_off = own_off;
+    K.own = own_out; K.mir = mir_out; K.kept = kept_out; K.drop = drop_tol;
+    return launch_row_fill(A, h, nullptr, nullptr, samelow, mir_off, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &K, st);
+}
+
+extern "C" int nksr_packed_mirrors_compact(int32_t n, const uint64_t* mir_staged, const int32_t* mir_off, const int32_t* kept_mir,
+                                           const int32_t* kept_off, uint64_t* mir_dense, void* stream) {
+    if (n <= 0) return NKSR_OK;
+    if (!mir_staged || !mir_off || !kept_mir || !kept_off || !mir_dense) return nksr_set_error(NKSR_ERR_ARG, "NULL arrays");
+    hipLaunchKernelGGL(k_pk_compact, dim3(nksr_blocks((int64_t)n * 16, 256)), dim3(256), 0, (hipStream_t)stream, n, mir_staged, mir_off,
+                       kept_mir, kept_off, mir_dense);
+    NKSR_CHECK_LAUNCH();
+    return NKSR_OK;
+}
+
+extern "C" int nksr_packed_row_lengths(int32_t n, const uint64_t* mir_sorted, int64_t n_mir, const int32_t* kept, const int32_t* old_of_new,
+                                       int32_t* runs_out, int32_t* lens_out, void* stream) {
+    if (n <= 0) return NKSR_OK;
+    if ((n_mir > 0 && !mir_sorted) || !kept || !old_of_new || !runs_out || !lens_out) return nksr_set_error(NKSR_ERR_ARG, "NULL arrays");
+    if (n_mir < 0 || n_mir >= ((int64_t)1 << 31)) return nksr_set_error(NKSR_ERR_ARG, "bad mirror count");
+    hipStream_t st = (hipStream_t)stream;
+    NKSR_CHECK_HIP(hipMemsetAsync(runs_out, 0, 2 * (size_t)n * sizeof(int32_t), st));
+    if (n_mir > 0) hipLaunchKernelGGL(k_pk_runs, dim3(nksr_blocks(n_mir, 256)), dim3(256), 0, st, mir_sorted, (int)n_mir, n, runs_out);
+    hipLaunchKernelGGL(k_pk_lens, dim3(nksr_blocks(n, 256)), dim3(256), 0, st, n, (const int32_t*)runs_out, kept, old_of_new, lens_out);
+    NKSR_CHECK_LAUNCH();
+    return NKSR_OK;
+}
+
+extern "C" int nksr_packed_rows(int32_t n, const uint64_t* mir_sorted, const int32_t* runs, const uint32_t* own, const int32_t* own_off,
+                                const int32_t* samelow, const int32_t* kept, const int32_t* old_of_new, const int32_t* packed_rowptr,
+                                const float* diag, uint32_t* packed_out, float* dis_out, void* stream) {
+    if (n <= 0) return NKSR_OK;
+    if (!runs || !own || !own_off || !samelow || !kept || !old_of_new || !packed_rowptr || !diag || !packed_out || !dis_out)
+        return nksr_set_error(NKSR_ERR_ARG, "NULL arrays");
+    hipLaunchKernelGGL(k_pk_rows, dim3(nksr_blocks((int64_t)n * 16, 256)), dim3(256), 0, (hipStream_t)stream, n, mir_sorted, runs, own, own_off,
+                       samelow, kept, old_of_new, packed_rowptr, diag, packed_out, dis_out);
+    NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
 

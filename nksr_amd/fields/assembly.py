@@ -131,3 +131,63 @@ def assemble(fld, pos_xyz, normal_xyz, normal_value, pos_weight, normal_weight, 
         fld.nnz = nnz
     del keep
     return rowptr, cols, vals, diag, b
+
+
+def assemble_packed(fld, reg_weight, coarse_from, fused_op, old_of_new, new_of_old, local_col, drop):
+    """The packed (format 1) diagonal block of the levels >= ``coarse_from`` straight from the row fill (csrc/assemble.hip,
+    nksr_assemble_packed): the drop test runs where an entry is formed, so neither the fp32 CSR of the block nor the mirrors of the
+    dropped entries exist.  ``old_of_new`` / ``new_of_old``: the segment-major renumbering (int32), ``local_col`` = new_of_old -
+    seg_base[segment].  Returns (packed, packed_rowptr, dis, kept, nnz, diag): the arrays nksr_coarse_pack makes of the CSR, word for
+    word, the structural entry count of the block, and its diagonal in the old order."""
+    dev = fld.device
+    c0 = int(coarse_from)
+    hier = fld._coarse_hier(c0)
+    M = fld.svh.num_unknowns - fld.svh.offsets[c0]
+    if M == 0:
+        raise RuntimeError('empty hierarchy')
+    keep = []
+    sets = (SiteSetT * 2)()
+    nsets = _sets_from_operator(fld, fused_op, c0, sets, keep)
+    counts = torch.zeros((4, M + 1), dtype=torch.int32, device=dev)
+    rowcount, crosscount, samelow, indeg = counts[0], counts[1], counts[2], counts[3]
+    ws = torch.empty(int(_lib.lib.nksr_assemble_workspace_bytes(C.byref(hier))), dtype=torch.uint8, device=dev)
+    td = _tick('_', time.perf_counter())
+    call('nksr_assemble_count', C.byref(hier), ptr(ws), ptr(rowcount), ptr(crosscount), ptr(samelow), ptr(indeg), stream())
+    n_up, n_mir = [int(v) for v in counts[:2].sum(dim=1, dtype=torch.int64).tolist()]
+    td = _tick('asm:count', td)
+    nnz = 2 * n_up + M
+    if nnz >= 2 ** 31 - 4096:
+        raise RuntimeError('coarse block too large (M=%d, nnz=%d >= 2^31)' % (M, nnz))
+    own_off = ops.exclusive_sum_i32(samelow + rowcount)        # (entry M of both is 0)
+    mir_off = ops.exclusive_sum_i32(crosscount)
+    own = torch.empty(max(2 * n_up - n_mir, 1), dtype=torch.int32, device=dev)     # same-level lower (= same-level upper) + own upper
+    mir = torch.empty(max(n_mir, 1), dtype=torch.int64, device=dev)
+    kept = torch.empty((3, M + 1), dtype=torch.int32, device=dev)
+    kept[:, M] = 0
+    diag = torch.empty(M, dtype=torch.float32, device=dev)
+    split_bytes = int(_lib.lib.nksr_assemble_split_bytes(C.byref(hier), sum(int(sets[i].n) * int(sets[i].ncomp) for i in range(nsets))))
+    split = torch.empty(split_bytes, dtype=torch.uint8, device=dev) if split_bytes else None
+    call('nksr_assemble_packed', C.byref(hier), sets, nsets, float(reg_weight), ptr(ws), ptr(samelow), ptr(mir_off), ptr(own_off),
+         ptr(new_of_old), ptr(local_col), float(drop), ptr(diag), ptr(own), ptr(mir), ptr(kept), ptr(split), split_bytes, stream())
+    td = _tick('asm:blocks+fill', td)
+    del split, ws, keep
+    kept_off = ops.exclusive_sum_i32(kept[2])
+    n_kept_mir = int(kept_off[M].item())
+    dense = torch.empty(n_kept_mir, dtype=torch.int64, device=dev)
+    if n_kept_mir:
+        call('nksr_packed_mirrors_compact', M, ptr(mir), ptr(mir_off), ptr(kept[2]), ptr(kept_off), ptr(dense), stream())
+    del mir
+    srt = ops.sort_keys(dense, begin_bit=32, end_bit=32 + ops._bits(M))          # stable, destination-row bits only
+    del dense
+    runs = torch.empty(2 * M, dtype=torch.int32, device=dev)
+    lens = torch.empty(M + 1, dtype=torch.int32, device=dev)
+    lens[M:] = 0
+    call('nksr_packed_row_lengths', M, ptr(srt), n_kept_mir, ptr(kept), ptr(old_of_new), ptr(runs), ptr(lens), stream())
+    prow = ops.exclusive_sum_i32(lens)
+    n_kept = int(prow[M].item())
+    packed = torch.empty(max(n_kept, 1), dtype=torch.int32, device=dev)
+    dis = torch.empty(M, dtype=torch.float32, device=dev)
+    call('nksr_packed_rows', M, ptr(srt), ptr(runs), ptr(own), ptr(own_off), ptr(samelow), ptr(kept), ptr(old_of_new), ptr(prow),
+         ptr(diag), ptr(packed), ptr(dis), stream())
+    td = _tick('asm:mirrors+pack', td)
+    return packed, prow, dis, n_kept, nnz, diag

@@ -71,14 +71,15 @@ def varying_bits(keys, level=None):
     return max(1, int((keys ^ keys[:1]).max()).bit_length())
 
 
-def sort_keys(keys, end_bit=None, level=None):
-    """Ascending radix sort of non-negative int64 keys (``level``: they are Morton keys of that hierarchy level, see key_hint)."""
+def sort_keys(keys, end_bit=None, level=None, begin_bit=0):
+    """Ascending radix sort of non-negative int64 keys (``level``: they are Morton keys of that hierarchy level, see key_hint).
+    ``begin_bit`` > 0: stable sort on the bits [begin_bit, end_bit) alone -- the bits below ride along as payload."""
     n = keys.numel()
     out = torch.empty_like(keys)
     if n:
         if end_bit is None:
             end_bit = varying_bits(keys, level)
-        with_tmp('nksr_sort_keys_u64', keys.device, ptr(keys), ptr(out), n, 0, int(end_bit), stream())
+        with_tmp('nksr_sort_keys_u64', keys.device, ptr(keys), ptr(out), n, int(begin_bit), int(end_bit), stream())
     return out
 
 
