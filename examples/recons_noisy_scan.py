@@ -23,7 +23,8 @@ if __name__ == '__main__':
     reconstructor = nksr.Reconstructor(device)
     field = reconstructor.reconstruct(input_xyz, input_normal, preprocess_fn=clean, voxel_size=0.02)
     mesh = field.extract_dual_mesh(mise_iter=1)
+    mesh = mesh.smooth(5)                       # five Taubin pairs take the lattice-frequency ripple out without shrinking the sphere
 
-    nksr.utils.write_ply_mesh('recons_noisy_scan.ply', mesh.v, mesh.f)
+    nksr.utils.write_ply_mesh('recons_noisy_scan.ply', mesh.v, mesh.f, normals=mesh.vertex_normals())
     r = torch.linalg.norm(mesh.v, dim=1)
     print('V=%d F=%d radius %.4f .. %.4f -> recons_noisy_scan.ply' % (mesh.v.shape[0], mesh.f.shape[0], float(r.min()), float(r.max())))

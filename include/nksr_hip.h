@@ -822,6 +822,62 @@ int nksr_topo_compact_mark(const void* faces, int faces_int64, int64_t nf, int64
 int nksr_topo_compact_faces(const void* faces, int faces_int64, int64_t nf, int64_t nv, const int32_t* face_flags, const int32_t* face_offsets,
                             const int32_t* vertex_flags, const int32_t* vertex_offsets, void* faces_out, int64_t* vertex_map_out, void* stream);
 
+/* ---- mesh geometry (nksr_amd/mesh_geometry.py: MeshGeometry; csrc/meshgeom.hip) ----------------------------
+ * The vertex-centred view of the topology's edge table and what is summed over it: vertex normals, barycentric vertex areas, angle
+ * defect, cotangent mean curvature, Laplacian / Taubin smoothing.  Faces, validity and the limits as in the topology section; n_edges
+ * < 2^31, so that the 2 E directed entries fit the uint32 row starts.  Positions `v` are [nv, 3] fp32 (v_float64 = 0) or fp64
+ * (v_float64 != 0) and are read in that precision; everything computed and stored is fp64.  No floating-point atomic: every sum runs
+ * in the order of its sorted row, so every array repeats bit for bit.
+ * Build: nksr_geom_directed_keys, nksr_sort_pairs_u64_u32 (end_bit = 32 + bit_length(nv)), nksr_geom_adjacency; for the corner rows
+ * nksr_geom_corner_keys, nksr_sort_pairs_u64_u32 (end_bit = bit_length(nv); stable: a row's corners ascend), nksr_geom_corner_rows. */
+#define NKSR_GEOM_INTERIOR 0        /* vertex kinds: referenced, on no boundary edge                            */
+#define NKSR_GEOM_ON_BOUNDARY 1     /* on at least one edge of class NKSR_TOPO_BOUNDARY                         */
+#define NKSR_GEOM_UNREFERENCED 2    /* named by no valid face                                                   */
+#define NKSR_GEOM_FIXED 0           /* boundary modes of the smoothing step: boundary vertices stay             */
+#define NKSR_GEOM_CURVE 1           /* a boundary vertex averages its neighbours over boundary edges only        */
+#define NKSR_GEOM_FREE 2            /* no special case                                                          */
+#define NKSR_GEOM_WEIGHT_ANGLE 0    /* vertex normal = sum of corner angle * unit face normal                   */
+#define NKSR_GEOM_WEIGHT_AREA 1     /* ... of face area * unit face normal                                      */
+/* per unique edge (a, b) of edges [E, 2] two pairs: keys (a << 32) | b and (b << 32) | a, both with id = the edge; [2 E] each */
+int nksr_geom_directed_keys(const int32_t* edges, int64_t n_edges, int64_t nv, uint64_t* keys_out, uint32_t* ids_out, void* stream);
+/* from the SORTED pairs: start_out [nv + 1] (row of vertex v = [start[v], start[v + 1]), by lower bound; start[nv] = 2 E),
+ * neighbour_out [2 E] (ascending inside a row), neighbour_edge_out [2 E] the edge of the entry, neighbour_class_out [2 E] its
+ * NKSR_TOPO_* class, vertex_kind_out [nv] NKSR_GEOM_* */
+int nksr_geom_adjacency(const uint64_t* keys_sorted, const uint32_t* edge_ids_sorted, int64_t n_edges, int64_t nv, const uint8_t* vertex_ref,
+                        const uint8_t* edge_class, uint32_t* start_out, int32_t* neighbour_out, int32_t* neighbour_edge_out,
+                        uint8_t* neighbour_class_out, uint8_t* vertex_kind_out, void* stream);
+/* per corner c = 3 f + k: key = its vertex, or nv for a corner of an invalid face (sorts behind every vertex); id = c; [3 nf] each */
+int nksr_geom_corner_keys(const void* faces, int faces_int64, int64_t nf, int64_t nv, const uint8_t* face_valid, uint64_t* keys_out,
+                          uint32_t* ids_out, void* stream);
+/* start_out [nv + 1] of the SORTED corner keys; start[nv] = the number of corners of valid faces */
+int nksr_geom_corner_rows(const uint64_t* keys_sorted, int64_t n_half, int64_t nv, uint32_t* start_out, void* stream);
+/* per face: angle_out / cot_out [nf, 3] of corner k (atan2(|e1 x e2|, e1 . e2) and e1 . e2 / |e1 x e2| of the two edges leaving it),
+ * normal_out [nf, 3] unit (0 for a face without area), area_out [nf]; an invalid face writes zeros everywhere */
+int nksr_geom_faces(const void* v, int v_float64, int64_t nv, const void* faces, int faces_int64, int64_t nf, const uint8_t* face_valid,
+                    double* angle_out, double* cot_out, double* normal_out, double* area_out, void* stream);
+/* weight_out [E] = the sum, over the half-edges ids_sorted[edge_start[e] .. edge_start[e + 1]) in that order, of the cotangent of the
+ * corner opposite (half-edge 3 f + k: corner (k + 2) % 3 of f): every valid face on the edge, non-manifold edges included */
+int nksr_geom_edge_weights(const uint32_t* ids_sorted, const uint32_t* edge_start, int64_t n_edges, int64_t nf, const double* cot,
+                           double* weight_out, void* stream);
+/* one gather over the corner row of every vertex; each output optional (NULL), not all: normal_out [nv, 3] = the unit vector of
+ * sum weight * face normal (weight: NKSR_GEOM_WEIGHT_*; 0 where the sum vanishes), area_out [nv] = a third of the incident faces'
+ * areas, angle_sum_out [nv] = the sum of the incident corner angles */
+int nksr_geom_vertex_gather(const uint32_t* corner_start, const uint32_t* corner_ids, int64_t nv, int64_t nf, const double* angle,
+                            const double* face_normal, const double* face_area, int weighting, double* normal_out, double* area_out,
+                            double* angle_sum_out, void* stream);
+/* one gather over the adjacency row: laplacian_out [nv, 3] = (1 / 2 A_i) sum_j w_ij (x_j - x_i), mean_curvature_out [nv] =
+ * |laplacian| / 2 * sgn(-laplacian . vertex_normal); NaN where vertex_kind != NKSR_GEOM_INTERIOR or A_i = 0.  Each optional, not both. */
+int nksr_geom_curvature(const void* v, int v_float64, int64_t nv, const uint32_t* start, const int32_t* neighbour, const int32_t* neighbour_edge,
+                        int64_t n_edges, const double* edge_weight, const double* vertex_area, const double* vertex_normal,
+                        const uint8_t* vertex_kind, double* laplacian_out, double* mean_curvature_out, void* stream);
+/* n_steps Laplacian steps x <- x + w (mean of the row's neighbours - x) queued on the stream without a host synchronisation, over the
+ * two [nv, 3] fp64 buffers: step s reads x_a and writes x_b when s is even (w = w_even), the other way round when odd (w = w_odd);
+ * the result is in x_a for an even n_steps.  A vertex stays when it is NKSR_GEOM_UNREFERENCED, flagged in `fixed` [nv] (may be NULL),
+ * or NKSR_GEOM_ON_BOUNDARY under NKSR_GEOM_FIXED; under NKSR_GEOM_CURVE such a vertex averages its boundary-class entries only. */
+int nksr_geom_smooth(double* x_a, double* x_b, int64_t nv, const uint32_t* start, const int32_t* neighbour, int64_t n_edges,
+                     const uint8_t* neighbour_class, const uint8_t* vertex_kind, const uint8_t* fixed, int boundary, int64_t n_steps,
+                     double w_even, double w_odd, void* stream);
+
 /* ---- normal orientation without sensors (csrc/orient.hip; nksr_amd/orient.py orient_graph) -------------
  * Hoppe et al. 1992: the minimum spanning forest of the k-nearest-neighbour graph under the weight 1 - |n_i . n_j|, sign flips
  * propagated along it.  DEFINITION (restated in tests/orient_ref.py; every output is a function of the input alone):

@@ -35,6 +35,19 @@ class MeshingResult:
         v, f, c, _ = self.topology().remove_small_components(min_faces, min_area, min_area_ratio, keep_largest, connectivity, self.c)
         return MeshingResult(v, f, c)
 
+    def geometry(self):
+        """``MeshGeometry`` of this mesh (nksr_amd/mesh_geometry.py): adjacency, normals, curvature, smoothing."""
+        from ..mesh_geometry import MeshGeometry
+        return MeshGeometry(self.v, self.f)
+
+    def vertex_normals(self, weighting='angle'):
+        """[V, 3] unit vertex normals in the dtype of ``v`` (``MeshGeometry.vertex_normals``)."""
+        return self.geometry().vertex_normals(weighting)
+
+    def smooth(self, iterations, method='taubin', lam=0.5, mu=-0.53, boundary='fixed', fixed=None):
+        """A new ``MeshingResult`` with the vertices of ``MeshGeometry.smooth``; ``f`` and ``c`` are shared with this one."""
+        return MeshingResult(self.geometry().smooth(iterations, method, lam, mu, boundary, fixed), self.f, self.c)
+
 
 class BaseField:
     def __init__(self, svh):

@@ -21,6 +21,7 @@ from ._lib import METRIC_FIELDS, NN_BLOCK, call, ptr, stream, with_tmp
 from .density import bbox_center
 from .mesh_input import bbox_centre, faces, gpu_device, is64, normals32, recentre
 from .mesh_query import MeshQuery, mesh_occupancy  # noqa: F401  (re-exported: nksr.metrics.MeshQuery)
+from .mesh_geometry import MeshGeometry  # noqa: F401  (re-exported: nksr.metrics.MeshGeometry)
 from .mesh_topology import MeshTopology  # noqa: F401  (re-exported: nksr.metrics.MeshTopology)
 from .neighbours import PointGrid, PointPyramid, choose_cell_size
 

@@ -54,36 +54,48 @@ def load_point_cloud(path):
     return xyz, nrm, col, sen
 
 
-def write_ply_mesh(path, v, f, c=None):
+def write_ply_mesh(path, v, f, c=None, normals=None):
+    """Binary PLY; ``c`` [V, 3] colours in [0, 1] and ``normals`` [V, 3] (``MeshingResult.vertex_normals``) are optional."""
     v = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, np.float32)
     f = np.asarray(f.detach().cpu() if torch.is_tensor(f) else f, np.int32)
     with open(path, 'wb') as out:
         hdr = ['ply', 'format binary_little_endian 1.0', 'element vertex %d' % len(v), 'property float x',
                'property float y', 'property float z']
+        fields = [('p', '<f4', 3)]
+        if normals is not None:
+            hdr += ['property float nx', 'property float ny', 'property float nz']
+            fields.append(('n', '<f4', 3))
         if c is not None:
             hdr += ['property uchar red', 'property uchar green', 'property uchar blue']
+            fields.append(('c', 'u1', 3))
         hdr += ['element face %d' % len(f), 'property list uchar int vertex_indices', 'end_header']
         out.write(('\n'.join(hdr) + '\n').encode())
+        rec = np.empty(len(v), dtype=fields)
+        rec['p'] = v
+        if normals is not None:
+            rec['n'] = np.asarray(normals.detach().cpu() if torch.is_tensor(normals) else normals, np.float32)
         if c is not None:
-            c8 = (np.clip(np.asarray(c.detach().cpu() if torch.is_tensor(c) else c), 0, 1) * 255).astype(np.uint8)
-            rec = np.empty(len(v), dtype=[('p', '<f4', 3), ('c', 'u1', 3)])
-            rec['p'], rec['c'] = v, c8
-            out.write(rec.tobytes())
-        else:
-            out.write(v.astype('<f4').tobytes())
+            rec['c'] = (np.clip(np.asarray(c.detach().cpu() if torch.is_tensor(c) else c), 0, 1) * 255).astype(np.uint8)
+        out.write(rec.tobytes())
         rec = np.empty(len(f), dtype=[('n', 'u1'), ('i', '<i4', 3)])
         rec['n'], rec['i'] = 3, f
         out.write(rec.tobytes())
 
 
-def write_obj_mesh(path, v, f):
+def write_obj_mesh(path, v, f, normals=None):
     """Wavefront OBJ (what the reference's examples write through pycg.vis.to_file, examples/gis_app.py:55).  ``v`` may be float64 in
-    a projected coordinate system (1e5 .. 1e6 metres): positions are written with 6 decimals, not through fp32."""
+    a projected coordinate system (1e5 .. 1e6 metres): positions are written with 6 decimals, not through fp32.  ``normals`` [V, 3]
+    (optional) are written as ``vn`` lines and every face names them (``f a//a b//b c//c``)."""
     v = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, np.float64)
     f = np.asarray(f.detach().cpu() if torch.is_tensor(f) else f, np.int64) + 1
     with open(path, 'w') as out:
         out.write(''.join('v %.6f %.6f %.6f\n' % (p[0], p[1], p[2]) for p in v))
-        out.write(''.join('f %d %d %d\n' % (t[0], t[1], t[2]) for t in f))
+        if normals is None:
+            out.write(''.join('f %d %d %d\n' % (t[0], t[1], t[2]) for t in f))
+        else:
+            n = np.asarray(normals.detach().cpu() if torch.is_tensor(normals) else normals, np.float64)
+            out.write(''.join('vn %.6f %.6f %.6f\n' % (p[0], p[1], p[2]) for p in n))
+            out.write(''.join('f %d//%d %d//%d %d//%d\n' % (t[0], t[0], t[1], t[1], t[2], t[2]) for t in f))
 
 
 def warning_on_low_memory(threshold_mb):
