@@ -878,6 +878,59 @@ int nksr_geom_smooth(double* x_a, double* x_b, int64_t nv, const uint32_t* start
                      const uint8_t* neighbour_class, const uint8_t* vertex_kind, const uint8_t* fixed, int boundary, int64_t n_steps,
                      double w_even, double w_odd, void* stream);
 
+/* ---- mesh simplification (nksr_amd/mesh_simplify.py: MeshSimplifier; csrc/meshsimp.hip) ------------------
+ * Quadric vertex clustering on a uniform grid: the referenced vertices of one cell become one vertex, placed where the planes of the
+ * cluster's faces say; faces that lose a corner disappear.  Faces, validity and the limits as in the topology section; K < 2^31
+ * clusters.  Positions as in the geometry section; `origin` points at three HOST doubles.  Everything computed is fp64 and relative to
+ * the centre of the cluster's cell.  No floating-point atomic: every sum runs in the order of its sorted run, so every array repeats bit
+ * for bit.
+ * Build: nksr_topo_compact_mark with every face kept (vertex flags = referenced), nksr_simp_cell_keys, nksr_sort_pairs_u64_u32 (stable,
+ * over the varying key bits), nksr_simp_run_heads, nksr_exclusive_sum_i32, (read K), nksr_simp_clusters, nksr_simp_face_remap; for the
+ * duplicates two stable nksr_sort_pairs_u64_u32 (by key_c, then key_ab gathered into that order) and nksr_simp_flag_duplicates; for the
+ * corner rows of the clusters nksr_geom_corner_keys / nksr_geom_corner_rows over cluster_faces with nv = K; nksr_simp_place,
+ * nksr_simp_cluster_means; nksr_topo_compact_* over (representatives, cluster_faces, keep). */
+#define NKSR_SIMP_MAX_INDEX (1ll << 21)     /* cell indices per axis lie in [0, 2^21)                                  */
+#define NKSR_SIMP_GROUP 16          /* lanes that share one cluster in nksr_simp_place                          */
+#define NKSR_SIMP_QUADRIC 0         /* placement: the regularised quadric minimiser, clamped to the cell        */
+#define NKSR_SIMP_MEAN 1            /* ... the mean of the cluster's referenced vertices                        */
+/* per vertex: key = i_x << 42 | i_y << 21 | i_z with i = floor((double(x) - origin) / cell_size), an fp64 subtraction followed by an
+ * fp64 division; all ones where vertex_ref [nv] is 0 and where an index falls outside [0, NKSR_SIMP_MAX_INDEX) or is not a number --
+ * *misfits_out counts the latter (zeroed here).  id = the vertex; [nv] each. */
+int nksr_simp_cell_keys(const void* v, int v_float64, int64_t nv, const int32_t* vertex_ref, const double* origin, double cell_size,
+                        uint64_t* keys_out, uint32_t* ids_out, int64_t* misfits_out, void* stream);
+/* flags_out [nv + 1] = 1 at the first sorted position of every distinct key but the all-ones one, then a 0; its exclusive sum ends with K */
+int nksr_simp_run_heads(const uint64_t* keys_sorted, int64_t nv, int32_t* flags_out, void* stream);
+/* cluster_of_out [nv] = rank of the vertex's key among the distinct keys (-1: all ones); cluster_start_out [K + 1] = sorted position of
+ * the cluster's first vertex, at [K] the number of keyed vertices; cluster_key_out [K] */
+int nksr_simp_clusters(const uint64_t* keys_sorted, const uint32_t* ids_sorted, int64_t nv, const int32_t* flags, const int32_t* offsets,
+                       int64_t n_clusters, int32_t* cluster_of_out, uint32_t* cluster_start_out, uint64_t* cluster_key_out, void* stream);
+/* per face: cluster_faces_out [nf, 3] (the input's integer type) = the clusters of its corners in corner order, (0, 0, 0) for an invalid
+ * face; valid_out [nf]; survives_out [nf] = valid and three distinct clusters; with a < b < c the sorted triple of a surviving face
+ * key_ab_out = a << 32 | b and key_c_out = c, both 0 elsewhere (no surviving face has that pair); ids_out [nf] = the face;
+ * counts_out [2] int64 = invalid faces, collapsed faces (zeroed here; integer atomics) */
+int nksr_simp_face_remap(const void* faces, int faces_int64, int64_t nf, int64_t nv, const int32_t* cluster_of, void* cluster_faces_out,
+                         uint8_t* valid_out, uint8_t* survives_out, uint64_t* key_ab_out, uint64_t* key_c_out, uint32_t* ids_out,
+                         int64_t* counts_out, void* stream);
+/* order [nf] = the faces sorted stably by key_c and then stably by key_ab: keep_out[f] = survives[f] and not the same triple as the
+ * face before it in that order (of equal triples the lowest face index stays); *count_out = the duplicates (zeroed here) */
+int nksr_simp_flag_duplicates(const uint32_t* order, int64_t nf, const uint64_t* key_ab, const uint64_t* key_c, const uint8_t* survives,
+                              uint8_t* keep_out, int64_t* count_out, void* stream);
+/* representative_out [K, 3] fp64.  With centre = origin + (i + 0.5) cell_size of the cluster's key: mean = the mean of (x - centre) over
+ * vertex_ids_sorted[cluster_start[c] .. cluster_start[c + 1]) in that order.  NKSR_SIMP_QUADRIC: over the corners
+ * corner_ids[corner_start[c] .. corner_start[c + 1]) (corner 3 t + k: face t, whose unit normal n and area a are recomputed; a face
+ * without area adds nothing) A = sum a n n^T, b = sum a d n with d = -n . (p0 - centre); NKSR_SIMP_GROUP lanes take every 16th corner each
+ * and meet in the xor butterfly 8, 4, 2, 1.  x = (A + mu tau I)^-1 (-b + mu tau mean), tau = trace A, by a 3 x 3 Cholesky factorisation;
+ * x = mean when tau = 0 and under NKSR_SIMP_MEAN (the corner arrays may then be NULL).  Output: centre + clamp(x, -cell_size / 2,
+ * cell_size / 2).  0 < regularisation <= 1. */
+int nksr_simp_place(const void* v, int v_float64, int64_t nv, const void* faces, int faces_int64, int64_t nf, const uint32_t* corner_start,
+                    const uint32_t* corner_ids, const uint32_t* cluster_start, const uint32_t* vertex_ids_sorted, const uint64_t* cluster_key,
+                    int64_t n_clusters, const double* origin, double cell_size, double regularisation, int placement,
+                    double* representative_out, void* stream);
+/* mean_out [K, channels] fp64 = the mean of attr [nv, channels] (fp32, or fp64 with attr_float64 != 0) over every cluster's vertex run,
+ * summed in fp64 in the order of the run (ascending vertex index); one lane per entry */
+int nksr_simp_cluster_means(const void* attr, int attr_float64, int64_t nv, int64_t channels, const uint32_t* cluster_start,
+                            const uint32_t* vertex_ids_sorted, int64_t n_clusters, double* mean_out, void* stream);
+
 /* ---- normal orientation without sensors (csrc/orient.hip; nksr_amd/orient.py orient_graph) -------------
  * Hoppe et al. 1992: the minimum spanning forest of the k-nearest-neighbour graph under the weight 1 - |n_i . n_j|, sign flips
  * propagated along it.  DEFINITION (restated in tests/orient_ref.py; every output is a function of the input alone):

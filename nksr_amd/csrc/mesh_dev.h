@@ -1,8 +1,29 @@
-// Shared by the mesh kernels (csrc/metrics.hip, csrc/meshquery.hip, csrc/meshtopo.hip): the reader of an int32 or int64 face array
-// (``faces_int64`` of their entry points).  What an index outside [0, nv) means is each caller's business (face_corners, tp_face).
+// Shared by the mesh kernels (csrc/metrics.hip, csrc/meshquery.hip, csrc/meshtopo.hip, csrc/meshgeom.hip, csrc/meshsimp.hip): the reader
+// of an int32 or int64 face array (``faces_int64`` of their entry points).  What an index outside [0, nv) means is each caller's
+// business (face_corners); mesh_valid_face is the topology's notion, which the simplifier shares.
 #pragma once
 #include "common.h"
 
 __device__ __forceinline__ int64_t mesh_face_index(const void* faces, int is64, int64_t k) {
     return is64 ? ((const int64_t*)faces)[k] : (int64_t)((const int32_t*)faces)[k];
+}
+
+// fp64 vectors of the geometry and simplification kernels (csrc/meshgeom.hip, csrc/meshsimp.hip)
+struct gm_vec3 { double x, y, z; };
+__device__ __forceinline__ gm_vec3 gm_sub(gm_vec3 a, gm_vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ double gm_dot(gm_vec3 a, gm_vec3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ gm_vec3 gm_cross(gm_vec3 a, gm_vec3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+// vertex i of an fp32 (v_f64 = 0) or fp64 position array
+__device__ __forceinline__ gm_vec3 gm_pos(const void* v, int v_f64, int64_t i) {
+    if (v_f64) { const double* p = (const double*)v + i * 3; return {p[0], p[1], p[2]}; }
+    const float* p = (const float*)v + i * 3;
+    return {(double)p[0], (double)p[1], (double)p[2]};
+}
+
+// the corners of face j and whether it is VALID: every index inside [0, nv) and no two equal
+__device__ __forceinline__ bool mesh_valid_face(const void* faces, int is64, int64_t j, int64_t nv, int64_t c[3]) {
+    c[0] = mesh_face_index(faces, is64, j * 3);
+    c[1] = mesh_face_index(faces, is64, j * 3 + 1);
+    c[2] = mesh_face_index(faces, is64, j * 3 + 2);
+    return c[0] >= 0 && c[0] < nv && c[1] >= 0 && c[1] < nv && c[2] >= 0 && c[2] < nv && c[0] != c[1] && c[1] != c[2] && c[0] != c[2];
 }

@@ -15,16 +15,7 @@
 
 #define GEOM_BLOCK 256
 
-struct gm_vec3 { double x, y, z; };
-__device__ __forceinline__ gm_vec3 gm_sub(gm_vec3 a, gm_vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double gm_dot(gm_vec3 a, gm_vec3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ gm_vec3 gm_cross(gm_vec3 a, gm_vec3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-// vertex i of an fp32 (v_f64 = 0) or fp64 position array
-__device__ __forceinline__ gm_vec3 gm_pos(const void* v, int v_f64, int64_t i) {
-    if (v_f64) { const double* p = (const double*)v + i * 3; return {p[0], p[1], p[2]}; }
-    const float* p = (const float*)v + i * 3;
-    return {(double)p[0], (double)p[1], (double)p[2]};
-}
+// (gm_vec3, gm_sub, gm_dot, gm_cross, gm_pos: mesh_dev.h)
 __device__ __forceinline__ gm_vec3 gm_row(const double* x, int64_t i) { return {x[i * 3], x[i * 3 + 1], x[i * 3 + 2]}; }
 __device__ __forceinline__ void gm_store(double* x, int64_t i, gm_vec3 p) { x[i * 3] = p.x; x[i * 3 + 1] = p.y; x[i * 3 + 2] = p.z; }
 

@@ -13,10 +13,7 @@
 
 // the corners of face j; false for an invalid face (an index outside [0, nv), or two equal indices)
 __device__ __forceinline__ bool tp_face(const void* faces, int is64, int64_t j, int64_t nv, int64_t c[3]) {
-    c[0] = mesh_face_index(faces, is64, j * 3);
-    c[1] = mesh_face_index(faces, is64, j * 3 + 1);
-    c[2] = mesh_face_index(faces, is64, j * 3 + 2);
-    return c[0] >= 0 && c[0] < nv && c[1] >= 0 && c[1] < nv && c[2] >= 0 && c[2] < nv && c[0] != c[1] && c[1] != c[2] && c[0] != c[2];
+    return mesh_valid_face(faces, is64, j, nv, c);
 }
 // the key no edge has and that sorts behind every edge of a mesh of nv vertices, inside the 32 + bit_length(nv) sorted bits
 __device__ __forceinline__ uint64_t tp_sentinel(int64_t nv) { return ((uint64_t)nv << 32) | (uint64_t)nv; }

@@ -48,6 +48,13 @@ class MeshingResult:
         """A new ``MeshingResult`` with the vertices of ``MeshGeometry.smooth``; ``f`` and ``c`` are shared with this one."""
         return MeshingResult(self.geometry().smooth(iterations, method, lam, mu, boundary, fixed), self.f, self.c)
 
+    def simplify(self, cell_size=None, target_faces=None, **kw):
+        """A new ``MeshingResult`` from ``MeshSimplifier.simplify`` (nksr_amd/mesh_simplify.py): the vertices of one grid cell become
+        one, placed by the quadrics of its faces; ``c`` is averaged per cell.  ``kw``: origin, placement, regularisation, dedup."""
+        from ..mesh_simplify import MeshSimplifier
+        r = MeshSimplifier(self.v, self.f, self.c).simplify(cell_size=cell_size, target_faces=target_faces, **kw)
+        return MeshingResult(r.v2, r.f2, r.c2)
+
 
 class BaseField:
     def __init__(self, svh):
