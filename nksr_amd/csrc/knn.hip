@@ -1,28 +1,34 @@
-// Grid-hash k-nearest-neighbour kernels:
-//   k_knn_pca_normals  kNN-PCA normal estimation -- nksr.get_estimate_normal_preprocess_fn(knn, deg)
-//                      (reference call sites examples/recons_waymo.py:36, gis_app.py:41; CPU recipe
-//                      examples/recons_waymo_cpu.py:21-41)
-//   k_nearest_index    nearest input point of every query -- fields.PCNNField colour lookup
-//                      (examples/recons_colored_mesh.py:28)
-//   k_sdf_pyramid      signed distance of arbitrary queries to an oriented cloud from their k nearest reference points -- the
-//                      training ground truth ext.sdfgen.sdf_from_points (ext/sdfgen/sdf_from_points.cu:32-140 on top of the
-//                      kd-tree of ext/common/kdtree_cuda.cu; call sites models/loss.py:85, dataset/av_gt_geometry.py:72):
-//                      sign vote or IMLS; k_knn_mean_dist_pyramid = its adaptive_knn radius;
-//                      k_knn_query_pyramid = the neighbours themselves written out (nksr_amd/cloud.py).  k <= 32: candidates sorted in
-//                      registers, an octree over the grid searched in one launch (second half of this file) -- at EVERY scale: a single
-//                      grid is the octree with one level.  k_sdf_from_points / k_knn_mean_dist = the any-k path: ONE grid, bisection
-//                      (the host sends them k > 32 only)
-// The cloud is Morton-sorted by a uniform grid (cell size chosen by the host so that a 3^3 block
-// holds a few times k points); cells are contiguous point ranges found through the voxel hash.
-// EXACT selection without a per-thread heap: the k-th smallest squared distance is found by a
-// 32-step bisection on the float bit pattern (positive floats order like their bit patterns), each
-// step re-counting the candidates (L1/L2 resident).  fp32 distances decide everything except the few
-// candidates within a couple of ulps of that radius: those are ranked by their fp64 distance, so the
-// neighbour SET is the one an fp64 kd-tree search returns (an fp32-only rule swaps near-equidistant
-// neighbours against it: normals off by ~1e-3 at a few points, measured in round 2).  The covariance
-// is then accumulated in fp64 over that set.  One thread per query, queries in Morton order
-// (neighbouring lanes scan the same cells).  (The normals keep the bisection: their queries ARE the cloud -- always near -- and
-// the fp64 tie rule needs the candidates AT the k-th distance, which a fixed-size list does not hold.)
+// Neighbour search over a Morton-sorted cloud (nksr_amd/neighbours.py: PointGrid = the sorted points, the point range of every
+// occupied cell and the cell hash; PointPyramid = an octree of such levels over the same points).  What is in this file:
+//
+//   1. One grid, any k: the block walk and the bisection.
+//        knn_block        the cells c + [-R, R]^3 in a fixed order, every candidate handed to a visitor with knn_d2 of its offset
+//        knn_radius       smallest ring whose inscribed ball holds k points, then the EXACT k-th smallest squared distance by a 32-step
+//                         bisection on the float bit pattern (positive floats order like their bit patterns), each step re-counting
+//                         the block (L1/L2 resident): exact selection without a per-thread heap
+//        knn_visit        the k neighbours that radius defines, in walk order
+//      k_knn_pca_normals  nksr_knn_pca_normals (nksr_amd/normals.py, kNN-PCA normals: nksr.get_estimate_normal_preprocess_fn, CPU
+//                         recipe examples/recons_waymo_cpu.py:21-41): one thread per query -- every query when k > KW_CAP or no work
+//                         array is given, else the queries k_knn_pca_wave hands back.  fp32 distances decide everything except the
+//                         few candidates within a couple of ulps of the k-th distance: those are ranked by their fp64 distance, so
+//                         the neighbour SET is the one an fp64 kd-tree search returns (an fp32-only rule swaps near-equidistant
+//                         neighbours against it: normals off by ~1e-3 at a few points); mean and covariance in fp64 over that set.
+//                         (The normals keep the bisection: their queries ARE the cloud -- always near -- and the fp64 tie rule needs
+//                         the candidates AT the k-th distance, which a fixed-size list does not hold.)
+//      k_knn_pca_wave     the same, one wavefront per query over an LDS candidate list (the default of nksr_knn_pca_normals)
+//      k_nearest_index    nksr_nearest_index (PointGrid.nearest: the colour lookup of fields.PCNNField)
+//      k_sdf_from_points, k_knn_mean_dist      nksr_sdf_from_points, nksr_knn_mean_dist (ext.sdfgen with nb_points > 32, on plain grids)
+//   2. The two estimators of ext.sdfgen.sdf_from_points (SdfVote, SdfImls; reference ext/sdfgen/sdf_from_points.cu:32-140, call sites
+//      models/loss.py:85, dataset/av_gt_geometry.py:72), each stated once and fed by both searches.
+//   3. k <= 32: the register-list search.  TopK (the k nearest candidates sorted in registers), knn_scan, knn_rings (one grid scale,
+//      cells nearest first, box pruning).
+//   4. The octree: KnnPyramid, knn_descend, knn_topk_pyramid (every scale in one launch; a single grid is the octree with one level),
+//      k_pyramid_level (nksr_knn_pyramid_level builds a level), and on them k_sdf_pyramid (nksr_sdf_from_points_pyramid),
+//      k_knn_mean_dist_pyramid (nksr_knn_mean_dist_pyramid: the adaptive_knn radius of ext.sdfgen).
+//   5. Metric and query kernels: k_nn_metrics (nksr_nn_metrics, nksr_amd/metrics.py: exact 1-NN with the mesh-metric epilogue, the
+//      exhaustive knn_topk_all behind it), k_knn_query_pyramid (nksr_knn_query_pyramid, nksr_amd/cloud.py and orient.py: the k
+//      nearest written out), k_radius_count (nksr_radius_count: the 27 cells of a grid with cell >= radius).
+// Queries run in Morton order where they are the cloud itself: neighbouring lanes scan the same cells.
 #include "common.h"
 
 struct KnnGrid {
@@ -52,20 +58,63 @@ __device__ __forceinline__ float knn_d2(float ex, float ey, float ez) {
     return fmaf(ez, ez, fmaf(ey, ey, ex * ex));
 }
 
-// number of candidates with squared distance <= r2 inside the (2R+1)^3 block around cell c
-__device__ __forceinline__ int count_within(const KnnGrid& g, const float q[3], const int c[3], int R, float r2) {
-    int n = 0;
+// The (2R+1)^3 block of cells around cell c, walked in ONE order -- dx outer, dz inner, the points of a cell ascending -- and every
+// candidate p handed to f(index, ex, ey, ez, d2): e = q - p (the sign the estimators take it in), d2 = knn_d2(e).  The order is part
+// of the contract: the tie rule of knn_visit, the index tie-break of k_nearest_index and the fp64 sums of the normals depend on it.
+// SHELL: for R > 1 only the cells with |offset|_inf == R (the rings inside were walked before).
+template <bool SHELL = false, class F>
+__device__ __forceinline__ void knn_block(const KnnGrid& g, const float q[3], const int c[3], int R, F&& f) {
     for (int dx = -R; dx <= R; ++dx)
         for (int dy = -R; dy <= R; ++dy)
             for (int dz = -R; dz <= R; ++dz) {
+                if (SHELL && R > 1 && abs(dx) < R && abs(dy) < R && abs(dz) < R) continue;
                 const int ci = hash_find(g.hkeys, g.hvals, g.hcap, morton_biased(c[0] + dx, c[1] + dy, c[2] + dz, NKSR_BIAS0));
                 if (ci < 0) continue;
                 for (int k = g.start[ci]; k < g.end[ci]; ++k) {
-                    const float ex = g.xyz[k * 3] - q[0], ey = g.xyz[k * 3 + 1] - q[1], ez = g.xyz[k * 3 + 2] - q[2];
-                    n += knn_d2(ex, ey, ez) <= r2;
+                    const float ex = q[0] - g.xyz[k * 3], ey = q[1] - g.xyz[k * 3 + 1], ez = q[2] - g.xyz[k * 3 + 2];
+                    f(k, ex, ey, ez, knn_d2(ex, ey, ez));
                 }
             }
+}
+
+// number of candidates with squared distance <= r2 inside the (2R+1)^3 block around cell c
+__device__ __forceinline__ int count_within(const KnnGrid& g, const float q[3], const int c[3], int R, float r2) {
+    int n = 0;
+    knn_block(g, q, c, R, [&](int, float, float, float, float d2) { n += d2 <= r2; });
     return n;
+}
+
+// smallest ring R whose inscribed ball already holds k points (then the k nearest are inside its block), and r2 = the exact k-th
+// smallest squared distance: bisection on the bit pattern.  false: fewer than k points within max_ring cells.
+__device__ __forceinline__ bool knn_radius(const KnnGrid& g, const float q[3], const int c[3], int k, int max_ring, int& R, float& r2) {
+    float rmax2 = 0.f;
+    bool ok = false;
+    for (R = 1; R <= max_ring; ++R) {
+        const float rr = (float)R * g.cell;          // the ball of radius R*cell around q lies inside the (2R+1)^3 block around q's cell
+        rmax2 = rr * rr;
+        if (count_within(g, q, c, R, rmax2) >= k) { ok = true; break; }
+    }
+    if (!ok) return false;
+    unsigned lo = 0u, hi = __float_as_uint(rmax2);   // count(lo) may be < k, count(hi) >= k
+    while (lo < hi) {
+        const unsigned mid = lo + ((hi - lo) >> 1);
+        if (count_within(g, q, c, R, __uint_as_float(mid)) >= k) hi = mid; else lo = mid + 1;
+    }
+    r2 = __uint_as_float(lo);
+    return true;
+}
+
+// The neighbour set of radius r2: every candidate closer than r2 plus, of the ones AT r2, as many as still fit (walk order) --
+// exactly k, like a kd-tree search (ties have measure zero on real data).  f as in knn_block.
+template <typename F>
+__device__ __forceinline__ void knn_visit(const KnnGrid& g, const float q[3], const int c[3], int R, float r2, int k, F f) {
+    int ties_left = k;
+    knn_block(g, q, c, R, [&](int, float, float, float, float d2) { ties_left -= d2 < r2; });
+    knn_block(g, q, c, R, [&](int kk, float ex, float ey, float ez, float d2) {
+        const bool tie = d2 == r2 && ties_left > 0;
+        ties_left -= tie;
+        if (d2 < r2 || tie) f(kk, ex, ey, ez, d2);
+    });
 }
 
 // smallest eigenvector of a symmetric 3x3 matrix (cyclic Jacobi, fp64)
@@ -112,61 +161,36 @@ __global__ void __launch_bounds__(128) k_knn_pca_normals(KnnGrid g, int64_t n, i
     if (i >= n) return;
     if (todo && !todo[i]) return;          // (fallback pass: only the queries the wave-per-query kernel handed back)
     const float q[3] = {g.xyz[i * 3], g.xyz[i * 3 + 1], g.xyz[i * 3 + 2]};
-    int c[3];
+    int c[3], R;
+    float r2;
     cell_of(g, q, c);
-    // smallest ring whose inscribed ball already holds k points (then the k nearest are inside it)
-    int R = 1;
-    float rmax2 = 0.f;
-    bool ok = false;
-    for (; R <= max_ring; ++R) {
-        // the ball of radius R*cell around q lies inside the (2R+1)^3 block around q's cell
-        const float rr = (float)R * g.cell;
-        rmax2 = rr * rr;
-        if (count_within(g, q, c, R, rmax2) >= k) { ok = true; break; }
-    }
-    if (!ok) {   // fewer than k points within max_ring cells: isolated point
+    if (!knn_radius(g, q, c, k, max_ring, R, r2)) {   // fewer than k points within max_ring cells: isolated point
         valid[i] = 0;
         normal[i * 3] = normal[i * 3 + 1] = 0.f;
         normal[i * 3 + 2] = 1.f;
         radius2[i] = 0.f;
         return;
     }
-    // exact k-th smallest squared distance: bisection on the bit pattern
-    unsigned lo = 0u, hi = __float_as_uint(rmax2);   // count(lo) may be < k, count(hi) >= k
-    while (lo < hi) {
-        const unsigned mid = lo + ((hi - lo) >> 1);
-        if (count_within(g, q, c, R, __uint_as_float(mid)) >= k) hi = mid; else lo = mid + 1;
-    }
-    const float r2 = __uint_as_float(lo);
     // candidates with an fp32 distance well below r2 are neighbours; the ones within a few ulps of it are ranked in fp64
     const float r2_lo = r2 * (1.0f - 2e-6f), r2_hi = r2 * (1.0f + 2e-6f);
+    auto dist64 = [&](int kk) {
+        const double fx = (double)g.xyz[kk * 3] - (double)q[0], fy = (double)g.xyz[kk * 3 + 1] - (double)q[1],
+                     fz = (double)g.xyz[kk * 3 + 2] - (double)q[2];
+        return fx * fx + fy * fy + fz * fz;
+    };
     constexpr int AMB = 12;
     double amb[AMB];
     int n_amb = 0, n_in = 0;
-    for (int dx = -R; dx <= R; ++dx)
-        for (int dy = -R; dy <= R; ++dy)
-            for (int dz = -R; dz <= R; ++dz) {
-                const int ci = hash_find(g.hkeys, g.hvals, g.hcap, morton_biased(c[0] + dx, c[1] + dy, c[2] + dz, NKSR_BIAS0));
-                if (ci < 0) continue;
-                for (int kk = g.start[ci]; kk < g.end[ci]; ++kk) {
-                    const float px = g.xyz[kk * 3], py = g.xyz[kk * 3 + 1], pz = g.xyz[kk * 3 + 2];
-                    const float ex = px - q[0], ey = py - q[1], ez = pz - q[2];
-                    const float d32 = ex * ex + ey * ey + ez * ez;
-                    if (d32 < r2_lo) { ++n_in; continue; }
-                    if (d32 > r2_hi) continue;
-                    const double fx = (double)px - (double)q[0], fy = (double)py - (double)q[1], fz = (double)pz - (double)q[2];
-                    double d64 = fx * fx + fy * fy + fz * fz;
-                    if (n_amb < AMB) {          // insertion into the (tiny) ascending list
-                        int j = n_amb++;
-                        while (j > 0 && amb[j - 1] > d64) { amb[j] = amb[j - 1]; --j; }
-                        amb[j] = d64;
-                    } else if (d64 < amb[AMB - 1]) {
-                        int j = AMB - 1;
-                        while (j > 0 && amb[j - 1] > d64) { amb[j] = amb[j - 1]; --j; }
-                        amb[j] = d64;
-                    }
-                }
-            }
+    knn_block(g, q, c, R, [&](int kk, float, float, float, float d32) {
+        if (d32 < r2_lo) { ++n_in; return; }
+        if (d32 > r2_hi) return;
+        const double d64 = dist64(kk);
+        if (n_amb < AMB || d64 < amb[AMB - 1]) {          // insertion into the (tiny) ascending list: a full one drops its last
+            int j = n_amb < AMB ? n_amb++ : AMB - 1;
+            while (j > 0 && amb[j - 1] > d64) { amb[j] = amb[j - 1]; --j; }
+            amb[j] = d64;
+        }
+    });
     int need = k - n_in;                         // how many of the near-threshold candidates belong to the k nearest
     if (need > n_amb) need = n_amb;
     const double thr64 = need > 0 ? amb[need - 1] : -1.0;
@@ -175,28 +199,16 @@ __global__ void __launch_bounds__(128) k_knn_pca_normals(KnnGrid g, int64_t n, i
     int cnt = 0;
     for (int pass = 0; pass < 2; ++pass) {
         double cov[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-        for (int dx = -R; dx <= R; ++dx)
-            for (int dy = -R; dy <= R; ++dy)
-                for (int dz = -R; dz <= R; ++dz) {
-                    const int ci = hash_find(g.hkeys, g.hvals, g.hcap, morton_biased(c[0] + dx, c[1] + dy, c[2] + dz, NKSR_BIAS0));
-                    if (ci < 0) continue;
-                    for (int kk = g.start[ci]; kk < g.end[ci]; ++kk) {
-                        const float px = g.xyz[kk * 3], py = g.xyz[kk * 3 + 1], pz = g.xyz[kk * 3 + 2];
-                        const float ex = px - q[0], ey = py - q[1], ez = pz - q[2];
-                        const float d32 = ex * ex + ey * ey + ez * ez;
-                        if (d32 > r2_hi) continue;
-                        if (d32 >= r2_lo) {
-                            const double fx = (double)px - (double)q[0], fy = (double)py - (double)q[1], fz = (double)pz - (double)q[2];
-                            if (fx * fx + fy * fy + fz * fz > thr64) continue;
-                        }
-                        if (pass == 0) { m[0] += px; m[1] += py; m[2] += pz; ++cnt; }
-                        else {
-                            const double d0 = px - m[0], d1 = py - m[1], d2 = pz - m[2];
-                            cov[0][0] += d0 * d0; cov[0][1] += d0 * d1; cov[0][2] += d0 * d2;
-                            cov[1][1] += d1 * d1; cov[1][2] += d1 * d2; cov[2][2] += d2 * d2;
-                        }
-                    }
-                }
+        knn_block(g, q, c, R, [&](int kk, float, float, float, float d32) {
+            if (d32 > r2_hi || (d32 >= r2_lo && dist64(kk) > thr64)) return;
+            const float px = g.xyz[kk * 3], py = g.xyz[kk * 3 + 1], pz = g.xyz[kk * 3 + 2];
+            if (pass == 0) { m[0] += px; m[1] += py; m[2] += pz; ++cnt; }
+            else {
+                const double d0 = px - m[0], d1 = py - m[1], d2 = pz - m[2];
+                cov[0][0] += d0 * d0; cov[0][1] += d0 * d1; cov[0][2] += d0 * d2;
+                cov[1][1] += d1 * d1; cov[1][2] += d1 * d2; cov[2][2] += d2 * d2;
+            }
+        });
         if (pass == 0) { m[0] /= cnt; m[1] /= cnt; m[2] /= cnt; }
         else {
             cov[1][0] = cov[0][1]; cov[2][0] = cov[0][2]; cov[2][1] = cov[1][2];
@@ -393,18 +405,9 @@ __global__ void __launch_bounds__(128) k_nearest_index(KnnGrid g, const float* _
     float bd = 3.4e38f;
     for (int R = 1; R <= max_ring; ++R) {
         // scan the shell |offset|_inf == R (R = 1: the full 3^3 block)
-        for (int dx = -R; dx <= R; ++dx)
-            for (int dy = -R; dy <= R; ++dy)
-                for (int dz = -R; dz <= R; ++dz) {
-                    if (R > 1 && abs(dx) < R && abs(dy) < R && abs(dz) < R) continue;
-                    const int ci = hash_find(g.hkeys, g.hvals, g.hcap, morton_biased(c[0] + dx, c[1] + dy, c[2] + dz, NKSR_BIAS0));
-                    if (ci < 0) continue;
-                    for (int k = g.start[ci]; k < g.end[ci]; ++k) {
-                        const float ex = g.xyz[k * 3] - q[0], ey = g.xyz[k * 3 + 1] - q[1], ez = g.xyz[k * 3 + 2] - q[2];
-                        const float d = ex * ex + ey * ey + ez * ez;
-                        if (d < bd || (d == bd && k < best)) { bd = d; best = k; }
-                    }
-                }
+        knn_block<true>(g, q, c, R, [&](int k, float, float, float, float d) {
+            if (d < bd || (d == bd && k < best)) { bd = d; best = k; }
+        });
         // everything closer than R*cell has been seen
         const float rr = (float)R * g.cell;
         if (best >= 0 && bd <= rr * rr) break;
@@ -412,68 +415,69 @@ __global__ void __launch_bounds__(128) k_nearest_index(KnnGrid g, const float* _
     index[i] = best;
 }
 
-// ---- ext.sdfgen.sdf_from_points ---------------------------------------------------------------------------------------------
-// Ring search + bit-pattern bisection as above give the k-th smallest squared distance r2 of a query; the neighbour set is
-// every candidate closer than r2 plus, of the ones AT r2, as many as still fit (scan order): exactly k, like a kd-tree search
-// (ties have measure zero on real data).  The two estimators then need one pass (vote) or two (IMLS) over that set -- no index
-// lists, no sort.
+// ---- ext.sdfgen.sdf_from_points: the two estimators ---------------------------------------------------------------------------
+// Each over the k nearest reference points of a query x, stated once and fed by both searches: by knn_visit in walk order
+// (k_sdf_from_points, which finds the nearest neighbour by a running minimum) and from the TopK list nearest first (sdf_estimate,
+// whose nearest neighbour is the first occupied slot).  add() takes neighbour kk at offset e = x - p_kk, squared distance d2.
 //   vote (ComputeSDFKernel, sdf_from_points.cu:83-140): the nearest neighbour decides the magnitude -- |n.(x-p)| if x lies within
 //        stdv * ref_std[p] of it, else |x-p| -- and the majority of sign(n_k.(x-p_k)) over the k neighbours the sign
 //        (positive needs MORE than k/2 votes);
 //   IMLS (ComputeIMLSKernel, :32-81): sum_k w_k n_k.(x-p_k) / sum_k w_k,  w_k = exp(-(|x-p_k|^2 - min_j |x-p_j|^2) / stdv^2).
+// n . e with a FIXED rounding sequence, like knn_d2: two products, their sum, one fma.  The vote's value IS this number (|n.(x-p)| of
+// the nearest neighbour); left to the compiler, every kernel it is inlined into picked its own contraction of nx*ex + ny*ey + nz*ez
+// and the same query got another last bit from each of them.  (IMLS sums k weighted terms in an order that differs between the two
+// searches anyway, and keeps the plain expression.)
+__device__ __forceinline__ float sdf_dot(float nx, float ny, float nz, float ex, float ey, float ez) {
+#pragma clang fp contract(off)
+    const float s = nx * ex + ny * ey;
+    return fmaf(nz, ez, s);
+}
+struct SdfVote {
+    int npos = 0;
+    float sd = 0.f, g0[3] = {0.f, 0.f, 0.f};
+    // nearest: kk is the nearest neighbour (so far, for a caller that learns it on the way: the last such call stands)
+    __device__ __forceinline__ void add(const float* __restrict__ nrm, const float* __restrict__ ref_std, float stdv, int kk, float ex, float ey,
+                                        float ez, float d2, bool nearest) {
+        const float nx = nrm[kk * 3], ny = nrm[kk * 3 + 1], nz = nrm[kk * 3 + 2];
+        const float d = sdf_dot(nx, ny, nz, ex, ey, ez);
+        npos += d > 0.f;
+        if (nearest) {                            // the nearest neighbour sets the magnitude
+            const float len = sqrtf(d2);
+            if (len < stdv * (ref_std ? ref_std[kk] : 1.f)) {
+                sd = fabsf(d);
+                const float sg = d > 0.f ? 1.f : -1.f;
+                g0[0] = sg * nx; g0[1] = sg * ny; g0[2] = sg * nz;
+            } else {
+                sd = len;
+                g0[0] = ex / len; g0[1] = ey / len; g0[2] = ez / len;
+            }
+        }
+    }
+    __device__ __forceinline__ void finish(int k, int64_t i, float* __restrict__ sdf, float* __restrict__ grad) const {
+        const float sg = npos <= k / 2 ? -1.f : 1.f;
+        sdf[i] = sg * sd;
+        if (grad) { grad[i * 3] = sg * g0[0]; grad[i * 3 + 1] = sg * g0[1]; grad[i * 3 + 2] = sg * g0[2]; }
+    }
+};
+struct SdfImls {
+    float inv_s2, emin = 0.f, wsum = 0.f, acc = 0.f, gr[3] = {0.f, 0.f, 0.f};
+    __device__ __forceinline__ explicit SdfImls(float stdv) : inv_s2(1.f / (stdv * stdv)) {}
+    __device__ __forceinline__ void nearest(float d2min) { emin = d2min * inv_s2; }      // before the first add()
+    __device__ __forceinline__ void add(const float* __restrict__ nrm, int kk, float ex, float ey, float ez, float d2) {
+        const float nx = nrm[kk * 3], ny = nrm[kk * 3 + 1], nz = nrm[kk * 3 + 2];
+        const float w = expf(-d2 * inv_s2 + emin);
+        wsum += w;
+        acc += (nx * ex + ny * ey + nz * ez) * w;
+        gr[0] += nx * w; gr[1] += ny * w; gr[2] += nz * w;
+    }
+    __device__ __forceinline__ void finish(int64_t i, float* __restrict__ sdf, float* __restrict__ grad) const {
+        sdf[i] = acc / wsum;
+        if (grad) { grad[i * 3] = gr[0] / wsum; grad[i * 3 + 1] = gr[1] / wsum; grad[i * 3 + 2] = gr[2] / wsum; }
+    }
+};
+
+// Any k, one grid: knn_radius, then one pass over the neighbour set (vote) or two (IMLS) -- no index lists, no sort.
 // valid = 0: fewer than k reference points within max_ring cells (the host retries those queries on a coarser grid).
-// candidates of the (2R+1)^3 block strictly closer than r2
-__device__ __forceinline__ int count_closer(const KnnGrid& g, const float q[3], const int c[3], int R, float r2) {
-    int n = 0;
-    for (int dx = -R; dx <= R; ++dx)
-        for (int dy = -R; dy <= R; ++dy)
-            for (int dz = -R; dz <= R; ++dz) {
-                const int ci = hash_find(g.hkeys, g.hvals, g.hcap, morton_biased(c[0] + dx, c[1] + dy, c[2] + dz, NKSR_BIAS0));
-                if (ci < 0) continue;
-                for (int kk = g.start[ci]; kk < g.end[ci]; ++kk) {
-                    const float ex = g.xyz[kk * 3] - q[0], ey = g.xyz[kk * 3 + 1] - q[1], ez = g.xyz[kk * 3 + 2] - q[2];
-                    n += knn_d2(ex, ey, ez) < r2;
-                }
-            }
-    return n;
-}
-
-template <typename F>
-__device__ __forceinline__ void knn_visit(const KnnGrid& g, const float q[3], const int c[3], int R, float r2, int k, F f) {
-    int ties_left = k - count_closer(g, q, c, R, r2);        // of the candidates AT r2, as many as still fit
-    for (int dx = -R; dx <= R; ++dx)
-        for (int dy = -R; dy <= R; ++dy)
-            for (int dz = -R; dz <= R; ++dz) {
-                const int ci = hash_find(g.hkeys, g.hvals, g.hcap, morton_biased(c[0] + dx, c[1] + dy, c[2] + dz, NKSR_BIAS0));
-                if (ci < 0) continue;
-                for (int kk = g.start[ci]; kk < g.end[ci]; ++kk) {
-                    const float px = g.xyz[kk * 3], py = g.xyz[kk * 3 + 1], pz = g.xyz[kk * 3 + 2];
-                    const float d2 = knn_d2(px - q[0], py - q[1], pz - q[2]);
-                    bool take = d2 < r2;
-                    if (!take && d2 == r2 && ties_left > 0) { take = true; --ties_left; }
-                    if (take) f(kk, q[0] - px, q[1] - py, q[2] - pz, d2);
-                }
-            }
-}
-
-__device__ __forceinline__ bool knn_radius(const KnnGrid& g, const float q[3], const int c[3], int k, int max_ring, int& R, float& r2) {
-    float rmax2 = 0.f;
-    bool ok = false;
-    for (R = 1; R <= max_ring; ++R) {
-        const float rr = (float)R * g.cell;          // the ball of radius R*cell around q lies inside the (2R+1)^3 block around q's cell
-        rmax2 = rr * rr;
-        if (count_within(g, q, c, R, rmax2) >= k) { ok = true; break; }
-    }
-    if (!ok) return false;
-    unsigned lo = 0u, hi = __float_as_uint(rmax2);
-    while (lo < hi) {
-        const unsigned mid = lo + ((hi - lo) >> 1);
-        if (count_within(g, q, c, R, __uint_as_float(mid)) >= k) hi = mid; else lo = mid + 1;
-    }
-    r2 = __uint_as_float(lo);
-    return true;
-}
-
 __global__ void __launch_bounds__(128) k_sdf_from_points(KnnGrid g, const float* __restrict__ nrm, const float* __restrict__ ref_std,
                                                          const float* __restrict__ query, int64_t nq, int k, int max_ring, float stdv,
                                                          int imls, float* __restrict__ sdf, float* __restrict__ grad,
@@ -486,48 +490,22 @@ __global__ void __launch_bounds__(128) k_sdf_from_points(KnnGrid g, const float*
     cell_of(g, q, c);
     if (!knn_radius(g, q, c, k, max_ring, R, r2)) { valid[i] = 0; return; }
     valid[i] = 1;
-    float out = 0.f, gr[3] = {0.f, 0.f, 0.f};
+    float dmin = 3.4e38f;
     if (imls) {
-        float dmin = 3.4e38f;
         knn_visit(g, q, c, R, r2, k, [&](int, float, float, float, float d2) { dmin = fminf(dmin, d2); });
-        const float inv_s2 = 1.f / (stdv * stdv);
-        const float emin = dmin * inv_s2;
-        float wsum = 0.f, acc = 0.f;
-        knn_visit(g, q, c, R, r2, k, [&](int kk, float ex, float ey, float ez, float d2) {
-            const float nx = nrm[kk * 3], ny = nrm[kk * 3 + 1], nz = nrm[kk * 3 + 2];
-            const float w = expf(-d2 * inv_s2 + emin);
-            wsum += w;
-            acc += (nx * ex + ny * ey + nz * ez) * w;
-            gr[0] += nx * w; gr[1] += ny * w; gr[2] += nz * w;
-        });
-        out = acc / wsum;
-        gr[0] /= wsum; gr[1] /= wsum; gr[2] /= wsum;
+        SdfImls est(stdv);
+        est.nearest(dmin);
+        knn_visit(g, q, c, R, r2, k, [&](int kk, float ex, float ey, float ez, float d2) { est.add(nrm, kk, ex, ey, ez, d2); });
+        est.finish(i, sdf, grad);
     } else {
-        float dbest = 3.4e38f, sd = 0.f, g0[3] = {0.f, 0.f, 0.f};
-        int npos = 0;
+        SdfVote est;
         knn_visit(g, q, c, R, r2, k, [&](int kk, float ex, float ey, float ez, float d2) {
-            const float nx = nrm[kk * 3], ny = nrm[kk * 3 + 1], nz = nrm[kk * 3 + 2];
-            const float d = nx * ex + ny * ey + nz * ez;
-            npos += d > 0.f;
-            if (d2 < dbest) {                         // the nearest neighbour sets the magnitude
-                dbest = d2;
-                const float len = sqrtf(d2);
-                if (len < stdv * (ref_std ? ref_std[kk] : 1.f)) {
-                    sd = fabsf(d);
-                    const float sg = d > 0.f ? 1.f : -1.f;
-                    g0[0] = sg * nx; g0[1] = sg * ny; g0[2] = sg * nz;
-                } else {
-                    sd = len;
-                    g0[0] = ex / len; g0[1] = ey / len; g0[2] = ez / len;
-                }
-            }
+            const bool nearest = d2 < dmin;
+            if (nearest) dmin = d2;
+            est.add(nrm, ref_std, stdv, kk, ex, ey, ez, d2, nearest);
         });
-        const float sg = npos <= k / 2 ? -1.f : 1.f;
-        out = sg * sd;
-        gr[0] = sg * g0[0]; gr[1] = sg * g0[1]; gr[2] = sg * g0[2];
+        est.finish(k, i, sdf, grad);
     }
-    sdf[i] = out;
-    if (grad) { grad[i * 3] = gr[0]; grad[i * 3 + 1] = gr[1]; grad[i * 3 + 2] = gr[2]; }
 }
 
 // mean distance of every (sorted) reference point to its k nearest reference points, itself included (the adaptive_knn radius,
@@ -665,58 +643,31 @@ __device__ __forceinline__ int knn_rings(float cellsz, const float q[3], const i
     }
 }
 
-// the two estimators over the k nearest neighbours in `top` (nearest first)
+// the two estimators over the k nearest neighbours in `top`: nearest first, the nearest in slot KMAX - k
 template <int KMAX>
 __device__ __forceinline__ void sdf_estimate(const float* __restrict__ xyz, const float* __restrict__ nrm, const float* __restrict__ ref_std, const float q[3],
                                              const TopK<KMAX>& top, int k, float stdv, int imls, int64_t i, float* __restrict__ sdf,
                                              float* __restrict__ grad) {
-    float out = 0.f, gr[3] = {0.f, 0.f, 0.f};
     if (imls) {
-        const float inv_s2 = 1.f / (stdv * stdv);
-        float emin = 0.f, wsum = 0.f, acc = 0.f;
+        SdfImls est(stdv);
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             if (j < KMAX - k) continue;
-            if (j == KMAX - k) emin = top.d2[j] * inv_s2;                       // the nearest neighbour
+            if (j == KMAX - k) est.nearest(top.d2[j]);
             const int kk = top.idx[j];
-            const float ex = q[0] - xyz[kk * 3], ey = q[1] - xyz[kk * 3 + 1], ez = q[2] - xyz[kk * 3 + 2];
-            const float nx = nrm[kk * 3], ny = nrm[kk * 3 + 1], nz = nrm[kk * 3 + 2];
-            const float w = expf(-top.d2[j] * inv_s2 + emin);
-            wsum += w;
-            acc += (nx * ex + ny * ey + nz * ez) * w;
-            gr[0] += nx * w; gr[1] += ny * w; gr[2] += nz * w;
+            est.add(nrm, kk, q[0] - xyz[kk * 3], q[1] - xyz[kk * 3 + 1], q[2] - xyz[kk * 3 + 2], top.d2[j]);
         }
-        out = acc / wsum;
-        gr[0] /= wsum; gr[1] /= wsum; gr[2] /= wsum;
+        est.finish(i, sdf, grad);
     } else {
-        int npos = 0;
-        float sd = 0.f, g0[3] = {0.f, 0.f, 0.f};
+        SdfVote est;
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             if (j < KMAX - k) continue;
             const int kk = top.idx[j];
-            const float ex = q[0] - xyz[kk * 3], ey = q[1] - xyz[kk * 3 + 1], ez = q[2] - xyz[kk * 3 + 2];
-            const float nx = nrm[kk * 3], ny = nrm[kk * 3 + 1], nz = nrm[kk * 3 + 2];
-            const float d = nx * ex + ny * ey + nz * ez;
-            npos += d > 0.f;
-            if (j == KMAX - k) {                      // the nearest neighbour sets the magnitude
-                const float len = sqrtf(top.d2[j]);
-                if (len < stdv * (ref_std ? ref_std[kk] : 1.f)) {
-                    sd = fabsf(d);
-                    const float sg = d > 0.f ? 1.f : -1.f;
-                    g0[0] = sg * nx; g0[1] = sg * ny; g0[2] = sg * nz;
-                } else {
-                    sd = len;
-                    g0[0] = ex / len; g0[1] = ey / len; g0[2] = ez / len;
-                }
-            }
+            est.add(nrm, ref_std, stdv, kk, q[0] - xyz[kk * 3], q[1] - xyz[kk * 3 + 1], q[2] - xyz[kk * 3 + 2], top.d2[j], j == KMAX - k);
         }
-        const float sg = npos <= k / 2 ? -1.f : 1.f;
-        out = sg * sd;
-        gr[0] = sg * g0[0]; gr[1] = sg * g0[1]; gr[2] = sg * g0[2];
+        est.finish(k, i, sdf, grad);
     }
-    sdf[i] = out;
-    if (grad) { grad[i * 3] = gr[0]; grad[i * 3 + 1] = gr[1]; grad[i * 3 + 2] = gr[2]; }
 }
 
 // ---- every scale in one launch: an octree over the same Morton-sorted points ---------------------------------------------------------

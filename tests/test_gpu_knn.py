@@ -58,6 +58,64 @@ def test_knn_pca_normals_match_kdtree():
     assert ((view * n2.cpu().numpy()).sum(1) > 0).all()
 
 
+def _normal_clouds(case):
+    """(points, cell or None = choose_cell_size, the values `todo` must hold, number of leading sphere points)"""
+    from nksr_amd import utils
+    sphere, _ = utils.synth_sphere(3000, 1.0, 0.002, seed=5)
+    if case == 'wave':
+        return sphere, None, {0}, 3000
+    if case == 'thread':            # cell 2.5: every 3^3 block holds all 3000 > KW_CAP points, the wavefront kernel hands every query back
+        return sphere, 2.5, {1}, 3000
+    blob = np.random.RandomState(11).randn(2500, 3) * 0.01 + np.array([3.0, 0.0, 0.0])      # its blocks overflow, the sphere's do not
+    return np.concatenate([sphere[:1500], blob]).astype(np.float32), None, {0, 1}, 1500
+
+
+@pytest.mark.parametrize('case', ['wave', 'thread', 'both'])
+def test_thread_per_query_normals_equal_the_wavefront_normals_and_take_what_it_hands_back(case):
+    """nksr_knn_pca_normals with a `todo` array (k_knn_pca_wave, then k_knn_pca_normals for the queries it handed back) and without
+    (k_knn_pca_normals for every query): the same valid flags and bit-equal k-th distances, and each within the bounds
+    test_gpu_pins.py::test_knn_neighbour_sets_equal_the_kdtree_sets holds the default path to against an fp64 kd-tree."""
+    from scipy.spatial import cKDTree
+    import parity_util as pu
+    from nksr_amd._lib import call, ptr, stream
+    from nksr_amd.neighbours import PointGrid, _grid_args, choose_cell_size
+    dev = torch.device('cuda:0')
+    knn = 16
+    xyz, cell, todo_values, n_sphere = _normal_clouds(case)
+    xt = torch.from_numpy(xyz).to(dev)
+    pg = PointGrid(xt, cell if cell else choose_cell_size(xt, knn))
+    n = len(xyz)
+    x64 = pg.xyz.cpu().numpy().astype(np.float64)
+    on_sphere = pg.perm.cpu().numpy() < n_sphere
+    d, nb = cKDTree(x64).query(x64, k=knn + 1)
+    a, b = d[:, knn - 1] ** 2, d[:, knn] ** 2
+    tie = b <= a * (1.0 + 4e-6)
+    p = x64[nb[:, :knn]]
+    c = p - p.mean(1, keepdims=True)
+    w, v = np.linalg.eigh(np.einsum('nki,nkj->nij', c, c))
+    good = (w[:, 1] - w[:, 0]) / w[:, 2] > 1e-2
+    assert good[on_sphere].mean() > 0.99
+    res = {}
+    for name in ('handed_back', 'thread_only'):
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        r2 = torch.empty(n, dtype=torch.float32, device=dev)
+        valid = torch.empty(n, dtype=torch.int32, device=dev)
+        todo = torch.full((n,), -1, dtype=torch.int32, device=dev) if name == 'handed_back' else None
+        call('nksr_knn_pca_normals', ptr(pg.xyz), n, *_grid_args(pg), knn, 6, ptr(nrm), ptr(r2), ptr(valid), ptr(todo), stream())
+        res[name] = (r2, valid)
+        if todo is not None:
+            assert set(np.unique(todo.cpu().numpy()).tolist()) == todo_values
+        assert bool((valid > 0).all())
+        r = r2.cpu().numpy().astype(np.float64)
+        pu.check('normals[%s,%s]:r2_vs_exact_kth' % (case, name), (np.abs(r - a) / a).max(), 4e-7)
+        assert (r[~tie] < b[~tie]).all() and (r >= a * (1 - 4e-7)).all()
+        ang = np.linalg.norm(np.cross(nrm.cpu().numpy().astype(np.float64), v[:, :, 0]), axis=1)
+        pu.check('normals[%s,%s]:normal_angle_well_conditioned' % (case, name), ang[good].max(), 2e-5)
+    pu.report('normals[%s]:near_ties' % case, fraction=float(tie.mean()))
+    assert torch.equal(res['handed_back'][1], res['thread_only'][1])
+    assert torch.equal(res['handed_back'][0].view(torch.int32), res['thread_only'][0].view(torch.int32))
+
+
 def test_preprocess_fn_drives_reconstruct():
     """sensor-only input through reconstruct(..., preprocess_fn=...) (examples/recons_waymo.py:30-37)."""
     import nksr

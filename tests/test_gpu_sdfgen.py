@@ -152,6 +152,50 @@ def test_more_neighbours_than_the_register_list_take_the_bisection_kernels(imls)
     assert (s[:1000] < 0).all() and (s[1000:] > 0).all()
 
 
+@pytest.mark.parametrize('k', [8, 20])
+def test_bisection_kernels_equal_the_register_list_kernels_on_the_same_grid(k):
+    """csrc/knn.hip k_knn_mean_dist / k_sdf_from_points (any k: bisection for the k-th distance, the estimators fed in scan order)
+    against k_knn_mean_dist_pyramid / k_sdf_pyramid (k <= 32: sorted register list, nearest first) on ONE grid, 4 rings.  Both take
+    their squared distances from the same fixed fma chain, so the neighbour sets and the summed terms are the same bits: what is
+    left is the order of summation.  (An fp64 kd-tree finds no query of these inputs whose k-th and (k+1)-th neighbours, or two
+    nearest, lie within 4e-6 relative of each other.)"""
+    from nksr_amd._lib import call, ptr, stream
+    from nksr_amd.neighbours import PointGrid, PointPyramid, _grid_args, choose_cell_size
+    dev = torch.device('cuda:0')
+    xyz, nrm = _cloud(3000, seed=3)
+    q = torch.from_numpy(_queries(xyz, nrm, 2000, seed=4)).to(dev)
+    ref = torch.from_numpy(xyz).to(dev)
+    pg = PointGrid(ref, choose_cell_size(ref, k))
+    pyr = PointPyramid(pg, max_levels=1)
+    ns = torch.from_numpy(nrm).to(dev)[pg.perm].contiguous()
+    n, m, rings = len(xyz), q.shape[0], 4
+    # mean distance to the k nearest (self queries)
+    md = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2)]
+    va = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2)]
+    call('nksr_knn_mean_dist', ptr(pg.xyz), n, *_grid_args(pg), k, rings, ptr(md[0]), ptr(va[0]), stream())
+    call('nksr_knn_mean_dist_pyramid', pyr.struct, n, k, rings, ptr(md[1]), ptr(va[1]), stream())
+    assert bool((va[0] == 1).all()) and bool((va[1] == 1).all())
+    rel = float(((md[0] - md[1]).abs().double() / md[1].double()).max())
+    pu.report('bisection vs list[k=%d] mean dist' % k, max_rel=rel)
+    assert rel <= 2.0 * (k - 1) * 2.0 ** -24          # two summation orders of the same k fp32 terms
+    # the two estimators
+    for imls in (0, 1):
+        s = [torch.empty(m, dtype=torch.float32, device=dev) for _ in range(2)]
+        g = [torch.empty((m, 3), dtype=torch.float32, device=dev) for _ in range(2)]
+        v = [torch.empty(m, dtype=torch.int32, device=dev) for _ in range(2)]
+        call('nksr_sdf_from_points', ptr(pg.xyz), ptr(ns), None, *_grid_args(pg), ptr(q), m, k, rings, 0.05, imls, ptr(s[0]), ptr(g[0]), ptr(v[0]),
+             stream())
+        call('nksr_sdf_from_points_pyramid', pyr.struct, ptr(ns), None, ptr(q), m, k, rings, 0.05, imls, ptr(s[1]), ptr(g[1]), ptr(v[1]), stream())
+        assert bool((v[0][:2000] == 1).all()) and bool((v[1][:2000] == 1).all())
+        both = ((v[0] > 0) & (v[1] > 0)).cpu().numpy()
+        sa, sb = s[0].cpu().numpy()[both], s[1].cpu().numpy()[both]
+        gd = (g[0] - g[1]).abs().amax(1).cpu().numpy()[both]
+        pu.report('bisection vs list[k=%d,%s]' % (k, 'imls' if imls else 'vote'), max_sdf_diff=float(np.abs(sa - sb).max()),
+                  max_grad_diff=float(gd.max()), compared=int(both.sum()), queries=m)
+        assert (np.abs(sa - sb) > 1e-5 + 1e-5 * np.abs(sb)).mean() <= 1e-3
+        assert (gd > 1e-4).mean() <= 2e-3
+
+
 def test_sdf_from_points_argument_errors():
     import ext
     dev = torch.device('cuda:0')
