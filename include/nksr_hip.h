@@ -59,6 +59,19 @@ int nksr_unique_u64(void* tmp, size_t* tmp_bytes, const uint64_t* in, uint64_t* 
                     int64_t n, void* stream);
 int nksr_exclusive_sum_i32(void* tmp, size_t* tmp_bytes, const int32_t* in, int32_t* out, int64_t n, void* stream);
 int nksr_exclusive_sum_i64(void* tmp, size_t* tmp_bytes, const int64_t* in, int64_t* out, int64_t n, void* stream);
+/* The run table of n SORTED keys (compared unsigned): the edges of a mesh, the clusters of a simplification, the voxels of a cloud.
+ * Keys >= none_from belong to no run (sorted, they are a tail); pass UINT64_MAX for "every key counts" -- the all-ones key is then
+ * never in a run.  Position i HEADS a run when its key is < none_from and differs from its predecessor's, or when i = 0.
+ * Sequence: nksr_run_counts_u64, nksr_exclusive_sum_i64 over the [blocks + 1] counts, (read n_runs = the scan's last entry),
+ * nksr_run_table_u64.  n < 2^32 (the starts are uint32); with run_of_out n_runs < 2^31.
+ * block_counts [nksr_run_blocks(n) + 1] = heads per block of 256 positions, then a 0.
+ * start_out [n_runs + 1] = the sorted position of every run's head, and at [n_runs] the position of the first key >= none_from, or n
+ * (0 for n = 0 and when no key is in a run); run_key_out [n_runs] or NULL = the runs' keys; run_of_out [n] or NULL = the run of every
+ * position, -1 for a key >= none_from. */
+int64_t nksr_run_blocks(int64_t n);                        /* ceil(n / 256), 0 for n <= 0 */
+int nksr_run_counts_u64(const uint64_t* keys_sorted, int64_t n, uint64_t none_from, int64_t* block_counts, void* stream);
+int nksr_run_table_u64(const uint64_t* keys_sorted, int64_t n, uint64_t none_from, const int64_t* block_offsets, int64_t n_runs,
+                       uint32_t* start_out, uint64_t* run_key_out, int32_t* run_of_out, void* stream);
 
 /* ---- hierarchy build/query (SparseFeatureHierarchy.build_point_splatting,
  *      models/nksr_net.py:62; grids[d].active_grid_coords models/loss.py:36) ------------ */
@@ -589,8 +602,8 @@ int nksr_radius_count(const float* xyz_sorted, int64_t n_ref, const int32_t* sta
                       int32_t cap, int exclude_self, const int32_t* self_index, int32_t* count_out, void* stream);
 
 /* ---- voxel reduction of a point cloud (csrc/cloud.hip; nksr_amd/cloud.py voxel_downsample) -----------------------------------
- * order [n] = point indices sorted by voxel key, start / end [n_vox] = the run of every voxel in it (nksr_site_ranges of the sorted
- * keys).  mean_xyz_out [n_vox, 3] and mean_attr_out [n_vox, C] = the mean of xyz [n, 3] and of attr [n, C] (C = 0: attr and
+ * order [n] = point indices sorted by voxel key, start / end [n_vox] = the run of every voxel in it (nksr_run_table_u64 of the sorted
+ * keys: start_out without its last entry, and without its first). mean_xyz_out [n_vox, 3] and mean_attr_out [n_vox, C] = the mean of xyz [n, 3] and of attr [n, C] (C = 0: attr and
  * mean_attr_out NULL; C <= NKSR_VOXEL_REDUCE_MAX_C) over every run, count_out [n_vox] its length.  Sums are fp64 in an order fixed by
  * (n_vox, start, end, group) alone -- a wavefront owns `group` consecutive voxels and walks their sorted positions 64 at a time, a
  * segmented tree inside the 64, tile after tile -- divided in fp64 and rounded once to fp32: no atomics, every run repeats bit for
@@ -760,7 +773,8 @@ int nksr_mesh_closest(const nksr_bvh_t* bvh, const float* query, int64_t nq, con
  * (half-edge ids 3 f + k fit uint32); beyond: NKSR_ERR_ARG.  Every result is an integer (or a min / max), so every array repeats
  * bit for bit; the one floating-point sum (component areas) goes through nksr_inclusive_sum_by_key_f64.
  * Build: nksr_topo_halfedge_keys, nksr_sort_pairs_u64_u32 (end_bit = 32 + bit_length(nv); stable, so half-edges of one edge stay in
- * ascending id order), nksr_topo_run_counts, nksr_exclusive_sum_i64, (read E), nksr_topo_edge_table, nksr_topo_edge_classes. */
+ * ascending id order), the run table of the sorted keys with none_from = the invalid faces' key (nksr_run_counts_u64,
+ * nksr_exclusive_sum_i64, (read E), nksr_run_table_u64: edge e = run e, edge_start = its start_out), nksr_topo_edge_classes. */
 #define NKSR_TOPO_MAX_FACES (1ll << 30)
 #define NKSR_TOPO_BOUNDARY 1        /* edge classes: one incident face                                        */
 #define NKSR_TOPO_INTERIOR 2        /* two, traversing the edge in opposite directions                         */
@@ -771,19 +785,13 @@ int nksr_mesh_closest(const nksr_bvh_t* bvh, const float* query, int64_t nq, con
  * writes the key (nv << 32) | nv, which sorts last.  face_valid_out [nf], vertex_ref_out [nv] (1: named by a valid face; zeroed here). */
 int nksr_topo_halfedge_keys(const void* faces, int faces_int64, int64_t nf, int64_t nv, uint64_t* keys_out, uint32_t* ids_out,
                             uint8_t* face_valid_out, uint8_t* vertex_ref_out, void* stream);
-/* run heads of the sorted keys: block_counts [nksr_topo_run_blocks(n_half) + 1] = heads per block of sorted positions, then a 0; its
- * exclusive sum (block_offsets) ends with E */
-int64_t nksr_topo_run_blocks(int64_t n_half);
-int nksr_topo_run_counts(const uint64_t* keys_sorted, int64_t n_half, int64_t nv, int64_t* block_counts, void* stream);
-/* edge e (ascending key): edge_v_out [E, 2] = (min, max); edge_start_out [E + 1] = sorted position of its first half-edge, and at
- * [E] the number of valid half-edges */
-int nksr_topo_edge_table(const uint64_t* keys_sorted, int64_t n_half, int64_t nv, const int64_t* block_offsets, int64_t n_edges,
-                         int32_t* edge_v_out, uint32_t* edge_start_out, void* stream);
-/* edge_count_out [E] incident valid faces; edge_class_out [E] NKSR_TOPO_*; face_adj_out [nf, 3]: the face across half-edge k, -1 on
- * a boundary, a non-manifold edge and an invalid face; totals_out [NKSR_TOPO_TOTALS] int64 (integer atomics) */
-int nksr_topo_edge_classes(const void* faces, int faces_int64, int64_t nf, int64_t nv, const uint32_t* ids_sorted, const uint32_t* edge_start,
-                           int64_t n_edges, const uint8_t* vertex_ref, int32_t* edge_count_out, uint8_t* edge_class_out, int32_t* face_adj_out,
-                           int64_t* totals_out, void* stream);
+/* edge e (ascending key) = run e of the sorted keys: edge_keys [E] the runs' keys, edge_start [E + 1] the sorted position of the edge's
+ * first half-edge and at [E] the number of valid half-edges.  edge_v_out [E, 2] = (min, max) of the key; edge_count_out [E] incident
+ * valid faces; edge_class_out [E] NKSR_TOPO_*; face_adj_out [nf, 3]: the face across half-edge k, -1 on a boundary, a non-manifold
+ * edge and an invalid face; totals_out [NKSR_TOPO_TOTALS] int64 (integer atomics) */
+int nksr_topo_edge_classes(const void* faces, int faces_int64, int64_t nf, int64_t nv, const uint32_t* ids_sorted, const uint64_t* edge_keys,
+                           const uint32_t* edge_start, int64_t n_edges, const uint8_t* vertex_ref, int32_t* edge_v_out, int32_t* edge_count_out,
+                           uint8_t* edge_class_out, int32_t* face_adj_out, int64_t* totals_out, void* stream);
 /* pairs_out [n_half, 2]: (face of sorted half-edge i, face of half-edge i + 1) when both lie on one edge, else (-1, -1): the faces
  * round an edge -- a non-manifold one too -- in a chain */
 int nksr_topo_face_pairs(const uint64_t* keys_sorted, const uint32_t* ids_sorted, int64_t n_half, int64_t nv, int32_t* pairs_out, void* stream);
@@ -885,7 +893,9 @@ int nksr_geom_smooth(double* x_a, double* x_b, int64_t nv, const uint32_t* start
  * the centre of the cluster's cell.  No floating-point atomic: every sum runs in the order of its sorted run, so every array repeats bit
  * for bit.
  * Build: nksr_topo_compact_mark with every face kept (vertex flags = referenced), nksr_simp_cell_keys, nksr_sort_pairs_u64_u32 (stable,
- * over the varying key bits), nksr_simp_run_heads, nksr_exclusive_sum_i32, (read K), nksr_simp_clusters, nksr_simp_face_remap; for the
+ * over the varying key bits), the run table of the sorted keys with none_from = all ones (nksr_run_counts_u64, nksr_exclusive_sum_i64,
+ * (read K), nksr_run_table_u64: cluster c = run c, cluster_start = its start_out, cluster_key = run_key_out, cluster_of[ids_sorted[i]] =
+ * run_of_out[i] -- ids_sorted is a permutation, an unreferenced vertex receives the -1), nksr_simp_face_remap; for the
  * duplicates two stable nksr_sort_pairs_u64_u32 (by key_c, then key_ab gathered into that order) and nksr_simp_flag_duplicates; for the
  * corner rows of the clusters nksr_geom_corner_keys / nksr_geom_corner_rows over cluster_faces with nv = K; nksr_simp_place,
  * nksr_simp_cluster_means; nksr_topo_compact_* over (representatives, cluster_faces, keep). */
@@ -898,13 +908,9 @@ int nksr_geom_smooth(double* x_a, double* x_b, int64_t nv, const uint32_t* start
  * *misfits_out counts the latter (zeroed here).  id = the vertex; [nv] each. */
 int nksr_simp_cell_keys(const void* v, int v_float64, int64_t nv, const int32_t* vertex_ref, const double* origin, double cell_size,
                         uint64_t* keys_out, uint32_t* ids_out, int64_t* misfits_out, void* stream);
-/* flags_out [nv + 1] = 1 at the first sorted position of every distinct key but the all-ones one, then a 0; its exclusive sum ends with K */
-int nksr_simp_run_heads(const uint64_t* keys_sorted, int64_t nv, int32_t* flags_out, void* stream);
-/* cluster_of_out [nv] = rank of the vertex's key among the distinct keys (-1: all ones); cluster_start_out [K + 1] = sorted position of
- * the cluster's first vertex, at [K] the number of keyed vertices; cluster_key_out [K] */
-int nksr_simp_clusters(const uint64_t* keys_sorted, const uint32_t* ids_sorted, int64_t nv, const int32_t* flags, const int32_t* offsets,
-                       int64_t n_clusters, int32_t* cluster_of_out, uint32_t* cluster_start_out, uint64_t* cluster_key_out, void* stream);
-/* per face: cluster_faces_out [nf, 3] (the input's integer type) = the clusters of its corners in corner order, (0, 0, 0) for an invalid
+/* (cluster_of [nv] = rank of the vertex's key among the distinct keys, -1: all ones; cluster_start [K + 1] = sorted position of the
+ * cluster's first vertex, at [K] the number of keyed vertices; cluster_key [K])
+ * per face: cluster_faces_out [nf, 3] (the input's integer type) = the clusters of its corners in corner order, (0, 0, 0) for an invalid
  * face; valid_out [nf]; survives_out [nf] = valid and three distinct clusters; with a < b < c the sorted triple of a surviving face
  * key_ab_out = a << 32 | b and key_c_out = c, both 0 elsewhere (no surviving face has that pair); ids_out [nf] = the face;
  * counts_out [2] int64 = invalid faces, collapsed faces (zeroed here; integer atomics) */

@@ -195,12 +195,8 @@ def voxel_runs(xyz, voxel_size):
     keys = torch.empty(n, dtype=torch.int64, device=dev)
     call('nksr_point_keys', ptr(xyz), n, inv_w0_f32(voxel_size), ptr(keys), stream())
     ks, order = ops.sort_pairs(keys, torch.arange(n, dtype=torch.int32, device=dev))
-    ukeys = ops.unique_sorted(ks)
-    nv = ukeys.numel()
-    start = torch.empty(nv, dtype=torch.int32, device=dev)
-    end = torch.empty(nv, dtype=torch.int32, device=dev)
-    call('nksr_site_ranges', ptr(ks), n, ptr(ukeys), nv, 0, ptr(start), ptr(end), stream())
-    return order, ukeys, start, end
+    _, s, ukeys, _ = ops.sorted_runs(ks, keys=True)          # (Morton keys are below 2^63: every key counts)
+    return order, ukeys, s[:-1], s[1:]
 
 
 def voxel_reduce(order, start, end, xyz, attr=None, nearest=False, group=0):

@@ -1,6 +1,7 @@
 // Shared by the mesh kernels (csrc/metrics.hip, csrc/meshquery.hip, csrc/meshtopo.hip, csrc/meshgeom.hip, csrc/meshsimp.hip): the reader
 // of an int32 or int64 face array (``faces_int64`` of their entry points).  What an index outside [0, nv) means is each caller's
-// business (face_corners); mesh_valid_face is the topology's notion, which the simplifier shares.
+// business (face_corners); mesh_valid_face is the topology's notion, which the simplifier shares.  Below it what the entry points of
+// meshtopo.hip, meshgeom.hip and meshsimp.hip share on the host: mesh_check_sizes and MESH_BLOCK / MESH_LAUNCH.
 #pragma once
 #include "common.h"
 
@@ -27,3 +28,17 @@ __device__ __forceinline__ bool mesh_valid_face(const void* faces, int is64, int
     c[2] = mesh_face_index(faces, is64, j * 3 + 2);
     return c[0] >= 0 && c[0] < nv && c[1] >= 0 && c[1] < nv && c[2] >= 0 && c[2] < nv && c[0] != c[1] && c[1] != c[2] && c[0] != c[2];
 }
+
+// ---- host side of the topology, geometry and simplification entry points: the limits of a mesh, one lane per item --------------
+static inline int mesh_check_sizes(const char* who, int64_t nv, int64_t nf) {
+    if (nv < 0 || nf < 0) return nksr_set_error(NKSR_ERR_ARG, "%s: negative size (nv=%lld, nf=%lld)", who, (long long)nv, (long long)nf);
+    if (nv >= (1ll << 31)) return nksr_set_error(NKSR_ERR_ARG, "%s: nv=%lld, at most 2^31 - 1 vertices", who, (long long)nv);
+    if (nf > NKSR_TOPO_MAX_FACES) return nksr_set_error(NKSR_ERR_ARG, "%s: %lld faces > 2^30", who, (long long)nf);
+    return NKSR_OK;
+}
+#define MESH_BLOCK 256
+#define MESH_LAUNCH(kernel, n, st, ...)                                                                                    \
+    do {                                                                                                                   \
+        hipLaunchKernelGGL(kernel, dim3(nksr_blocks((n), MESH_BLOCK)), dim3(MESH_BLOCK), 0, (st), __VA_ARGS__);             \
+        NKSR_CHECK_LAUNCH();                                                                                               \
+    } while (0)

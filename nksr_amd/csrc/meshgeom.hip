@@ -13,16 +13,14 @@
 #include "common.h"
 #include "mesh_dev.h"
 
-#define GEOM_BLOCK 256
-
 // (gm_vec3, gm_sub, gm_dot, gm_cross, gm_pos: mesh_dev.h)
 __device__ __forceinline__ gm_vec3 gm_row(const double* x, int64_t i) { return {x[i * 3], x[i * 3 + 1], x[i * 3 + 2]}; }
 __device__ __forceinline__ void gm_store(double* x, int64_t i, gm_vec3 p) { x[i * 3] = p.x; x[i * 3 + 1] = p.y; x[i * 3 + 2] = p.z; }
 
 // ---- 1. directed adjacency -------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_directed_keys(const int32_t* __restrict__ edges, int64_t ne, uint64_t* __restrict__ keys,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_directed_keys(const int32_t* __restrict__ edges, int64_t ne, uint64_t* __restrict__ keys,
                                                                    uint32_t* __restrict__ ids) {
-    const int64_t e = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t e = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (e >= ne) return;
     const uint64_t a = (uint64_t)(uint32_t)edges[e * 2], b = (uint64_t)(uint32_t)edges[e * 2 + 1];
     keys[e * 2] = (a << 32) | b;
@@ -33,9 +31,9 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_directed_keys(const int32_t
 
 // start[v] = the first sorted position whose key is >= v << shift, for v in [0, nv]: rows of equal (key >> shift), and at [nv] the
 // position of the first key behind every vertex (the sentinels of the corner list, or n)
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_row_starts(const uint64_t* __restrict__ keys, int64_t n, int64_t nv, int shift,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_row_starts(const uint64_t* __restrict__ keys, int64_t n, int64_t nv, int shift,
                                                                 uint32_t* __restrict__ start) {
-    const int64_t v = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t v = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (v > nv) return;
     const uint64_t target = (uint64_t)v << shift;
     int64_t lo = 0, hi = n;
@@ -47,10 +45,10 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_row_starts(const uint64_t* 
     start[v] = (uint32_t)lo;
 }
 
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_unpack(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ eids, int64_t n,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_unpack(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ eids, int64_t n,
                                                             const uint8_t* __restrict__ edge_class, int32_t* __restrict__ nbr,
                                                             int32_t* __restrict__ nbr_edge, uint8_t* __restrict__ nbr_class) {
-    const int64_t i = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (i >= n) return;
     const uint32_t e = eids[i];
     nbr[i] = (int32_t)(keys[i] & 0xFFFFFFFFull);
@@ -58,9 +56,9 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_unpack(const uint64_t* __re
     nbr_class[i] = edge_class[e];
 }
 
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_vertex_kind(const uint32_t* __restrict__ start, const uint8_t* __restrict__ nbr_class,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_vertex_kind(const uint32_t* __restrict__ start, const uint8_t* __restrict__ nbr_class,
                                                                  const uint8_t* __restrict__ vertex_ref, int64_t nv, uint8_t* __restrict__ kind) {
-    const int64_t v = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t v = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (v >= nv) return;
     int k = NKSR_GEOM_UNREFERENCED;
     if (vertex_ref[v]) {
@@ -72,10 +70,10 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_vertex_kind(const uint32_t*
 }
 
 // ---- 2. vertex -> corner incidence -----------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_corner_keys(const void* faces, int is64, int64_t nf, int64_t nv,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_corner_keys(const void* faces, int is64, int64_t nf, int64_t nv,
                                                                  const uint8_t* __restrict__ face_valid, uint64_t* __restrict__ keys,
                                                                  uint32_t* __restrict__ ids) {
-    const int64_t j = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t j = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (j >= nf) return;
     const bool ok = face_valid[j] != 0;
 #pragma unroll
@@ -86,10 +84,10 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_corner_keys(const void* fac
 }
 
 // ---- 3. per face -----------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_faces(const void* v, int v_f64, const void* faces, int is64, int64_t nf,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_faces(const void* v, int v_f64, const void* faces, int is64, int64_t nf,
                                                            const uint8_t* __restrict__ face_valid, double* __restrict__ angle,
                                                            double* __restrict__ cot, double* __restrict__ normal, double* __restrict__ area) {
-    const int64_t j = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t j = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (j >= nf) return;
     if (!face_valid[j]) {
 #pragma unroll
@@ -118,9 +116,9 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_faces(const void* v, int v_
 
 // ---- 4. per edge -----------------------------------------------------------------------------------------------------------------
 // half-edge h = 3 f + k runs corner k -> corner k + 1: the corner opposite is k + 2
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_edge_weights(const uint32_t* __restrict__ ids, const uint32_t* __restrict__ edge_start,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_edge_weights(const uint32_t* __restrict__ ids, const uint32_t* __restrict__ edge_start,
                                                                   int64_t ne, const double* __restrict__ cot, double* __restrict__ weight) {
-    const int64_t e = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t e = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (e >= ne) return;
     double w = 0.0;
     for (int64_t i = edge_start[e], end = edge_start[e + 1]; i < end; ++i) {
@@ -132,11 +130,11 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_edge_weights(const uint32_t
 }
 
 // ---- 5. per vertex ---------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_vertex_gather(const uint32_t* __restrict__ corner_start, const uint32_t* __restrict__ corner_ids,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_vertex_gather(const uint32_t* __restrict__ corner_start, const uint32_t* __restrict__ corner_ids,
                                                                    int64_t nv, const double* __restrict__ angle, const double* __restrict__ face_normal,
                                                                    const double* __restrict__ face_area, int weighting, double* __restrict__ normal_out,
                                                                    double* __restrict__ area_out, double* __restrict__ angle_out) {
-    const int64_t v = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t v = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (v >= nv) return;
     gm_vec3 n = {0.0, 0.0, 0.0};
     double a_sum = 0.0, t_sum = 0.0;
@@ -161,12 +159,12 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_vertex_gather(const uint32_
 }
 
 // lap = (1 / 2A) sum_j w_ij (x_j - x_i);  H = |lap| / 2 * sgn(-lap . n);  NaN off the interior and where A = 0
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_curvature(const void* pos, int v_f64, int64_t nv, const uint32_t* __restrict__ start,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_curvature(const void* pos, int v_f64, int64_t nv, const uint32_t* __restrict__ start,
                                                                const int32_t* __restrict__ nbr, const int32_t* __restrict__ nbr_edge,
                                                                const double* __restrict__ edge_weight, const double* __restrict__ vertex_area,
                                                                const double* __restrict__ normal, const uint8_t* __restrict__ kind,
                                                                double* __restrict__ lap_out, double* __restrict__ h_out) {
-    const int64_t v = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t v = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (v >= nv) return;
     const gm_vec3 xi = gm_pos(pos, v_f64, v);
     gm_vec3 s = {0.0, 0.0, 0.0};
@@ -192,11 +190,11 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_curvature(const void* pos, 
 // ---- 6. the smoothing step -------------------------------------------------------------------------------------------------------
 // A vertex stays (its row is copied) when it is unreferenced, flagged in `fixed`, or on a boundary edge under NKSR_GEOM_FIXED.  Under
 // NKSR_GEOM_CURVE a boundary vertex averages the neighbours it reaches over boundary-class edges only.  Uniform weights over the row.
-__global__ void __launch_bounds__(GEOM_BLOCK) k_geom_smooth_step(const double* __restrict__ x_in, double* __restrict__ x_out, int64_t nv,
+__global__ void __launch_bounds__(MESH_BLOCK) k_geom_smooth_step(const double* __restrict__ x_in, double* __restrict__ x_out, int64_t nv,
                                                                  const uint32_t* __restrict__ start, const int32_t* __restrict__ nbr,
                                                                  const uint8_t* __restrict__ nbr_class, const uint8_t* __restrict__ kind,
                                                                  const uint8_t* __restrict__ fixed, int boundary, double w) {
-    const int64_t v = (int64_t)blockIdx.x * GEOM_BLOCK + threadIdx.x;
+    const int64_t v = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (v >= nv) return;
     const gm_vec3 xi = gm_row(x_in, v);
     const int k = kind[v];
@@ -225,12 +223,6 @@ __global__ void __launch_bounds__(GEOM_BLOCK) k_geom_smooth_step(const double* _
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------
-static int gm_check_mesh(const char* who, int64_t nv, int64_t nf) {
-    if (nv < 0 || nf < 0) return nksr_set_error(NKSR_ERR_ARG, "%s: negative size (nv=%lld, nf=%lld)", who, (long long)nv, (long long)nf);
-    if (nv >= (1ll << 31)) return nksr_set_error(NKSR_ERR_ARG, "%s: nv=%lld, at most 2^31 - 1 vertices", who, (long long)nv);
-    if (nf > NKSR_TOPO_MAX_FACES) return nksr_set_error(NKSR_ERR_ARG, "%s: %lld faces > 2^30", who, (long long)nf);
-    return NKSR_OK;
-}
 // the unique edges of nf <= 2^30 faces: at most 3 * 2^30, and 2 E directed entries must fit the uint32 row starts
 static int gm_check_edges(const char* who, int64_t nv, int64_t ne) {
     if (nv < 0 || ne < 0) return nksr_set_error(NKSR_ERR_ARG, "%s: negative size (nv=%lld, n_edges=%lld)", who, (long long)nv, (long long)ne);
@@ -238,18 +230,13 @@ static int gm_check_edges(const char* who, int64_t nv, int64_t ne) {
     if (ne >= (1ll << 31)) return nksr_set_error(NKSR_ERR_ARG, "%s: n_edges=%lld, at most 2^31 - 1 edges", who, (long long)ne);
     return NKSR_OK;
 }
-#define GM_LAUNCH(kernel, n, st, ...)                                                                                      \
-    do {                                                                                                                   \
-        hipLaunchKernelGGL(kernel, dim3(nksr_blocks((n), GEOM_BLOCK)), dim3(GEOM_BLOCK), 0, (st), __VA_ARGS__);             \
-        NKSR_CHECK_LAUNCH();                                                                                               \
-    } while (0)
 
 extern "C" int nksr_geom_directed_keys(const int32_t* edges, int64_t n_edges, int64_t nv, uint64_t* keys_out, uint32_t* ids_out, void* stream) {
     int rc = gm_check_edges("geom directed keys", nv, n_edges);
     if (rc) return rc;
     if (n_edges == 0) return NKSR_OK;
     if (!edges || !keys_out || !ids_out) return nksr_set_error(NKSR_ERR_ARG, "geom directed keys: NULL arrays");
-    GM_LAUNCH(k_geom_directed_keys, n_edges, (hipStream_t)stream, edges, n_edges, keys_out, ids_out);
+    MESH_LAUNCH(k_geom_directed_keys, n_edges, (hipStream_t)stream, edges, n_edges, keys_out, ids_out);
     return NKSR_OK;
 }
 
@@ -263,65 +250,65 @@ extern "C" int nksr_geom_adjacency(const uint64_t* keys_sorted, const uint32_t* 
         return nksr_set_error(NKSR_ERR_ARG, "geom adjacency: NULL arrays");
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = 2 * n_edges;
-    GM_LAUNCH(k_geom_row_starts, nv + 1, st, keys_sorted, n, nv, 32, start_out);
-    if (n > 0) GM_LAUNCH(k_geom_unpack, n, st, keys_sorted, edge_ids_sorted, n, edge_class, neighbour_out, neighbour_edge_out, neighbour_class_out);
-    if (nv > 0) GM_LAUNCH(k_geom_vertex_kind, nv, st, start_out, neighbour_class_out, vertex_ref, nv, vertex_kind_out);
+    MESH_LAUNCH(k_geom_row_starts, nv + 1, st, keys_sorted, n, nv, 32, start_out);
+    if (n > 0) MESH_LAUNCH(k_geom_unpack, n, st, keys_sorted, edge_ids_sorted, n, edge_class, neighbour_out, neighbour_edge_out, neighbour_class_out);
+    if (nv > 0) MESH_LAUNCH(k_geom_vertex_kind, nv, st, start_out, neighbour_class_out, vertex_ref, nv, vertex_kind_out);
     return NKSR_OK;
 }
 
 extern "C" int nksr_geom_corner_keys(const void* faces, int faces_int64, int64_t nf, int64_t nv, const uint8_t* face_valid, uint64_t* keys_out,
                                      uint32_t* ids_out, void* stream) {
-    int rc = gm_check_mesh("geom corner keys", nv, nf);
+    int rc = mesh_check_sizes("geom corner keys", nv, nf);
     if (rc) return rc;
     if (nf == 0) return NKSR_OK;
     if (!faces || !face_valid || !keys_out || !ids_out) return nksr_set_error(NKSR_ERR_ARG, "geom corner keys: NULL arrays");
-    GM_LAUNCH(k_geom_corner_keys, nf, (hipStream_t)stream, faces, faces_int64, nf, nv, face_valid, keys_out, ids_out);
+    MESH_LAUNCH(k_geom_corner_keys, nf, (hipStream_t)stream, faces, faces_int64, nf, nv, face_valid, keys_out, ids_out);
     return NKSR_OK;
 }
 
 extern "C" int nksr_geom_corner_rows(const uint64_t* keys_sorted, int64_t n_half, int64_t nv, uint32_t* start_out, void* stream) {
     if (n_half < 0 || n_half % 3 != 0)
         return nksr_set_error(NKSR_ERR_ARG, "geom corner rows: n_half=%lld is not three times a face count", (long long)n_half);
-    int rc = gm_check_mesh("geom corner rows", nv, n_half / 3);
+    int rc = mesh_check_sizes("geom corner rows", nv, n_half / 3);
     if (rc) return rc;
     if (!start_out || (n_half > 0 && !keys_sorted)) return nksr_set_error(NKSR_ERR_ARG, "geom corner rows: NULL arrays");
-    GM_LAUNCH(k_geom_row_starts, nv + 1, (hipStream_t)stream, keys_sorted, n_half, nv, 0, start_out);
+    MESH_LAUNCH(k_geom_row_starts, nv + 1, (hipStream_t)stream, keys_sorted, n_half, nv, 0, start_out);
     return NKSR_OK;
 }
 
 extern "C" int nksr_geom_faces(const void* v, int v_float64, int64_t nv, const void* faces, int faces_int64, int64_t nf, const uint8_t* face_valid,
                                double* angle_out, double* cot_out, double* normal_out, double* area_out, void* stream) {
-    int rc = gm_check_mesh("geom faces", nv, nf);
+    int rc = mesh_check_sizes("geom faces", nv, nf);
     if (rc) return rc;
     if (nf == 0) return NKSR_OK;
     if (!v || !faces || !face_valid || !angle_out || !cot_out || !normal_out || !area_out) return nksr_set_error(NKSR_ERR_ARG, "geom faces: NULL arrays");
-    GM_LAUNCH(k_geom_faces, nf, (hipStream_t)stream, v, v_float64, faces, faces_int64, nf, face_valid, angle_out, cot_out, normal_out, area_out);
+    MESH_LAUNCH(k_geom_faces, nf, (hipStream_t)stream, v, v_float64, faces, faces_int64, nf, face_valid, angle_out, cot_out, normal_out, area_out);
     return NKSR_OK;
 }
 
 extern "C" int nksr_geom_edge_weights(const uint32_t* ids_sorted, const uint32_t* edge_start, int64_t n_edges, int64_t nf, const double* cot,
                                       double* weight_out, void* stream) {
-    int rc = gm_check_mesh("geom edge weights", 0, nf);
+    int rc = mesh_check_sizes("geom edge weights", 0, nf);
     if (rc) return rc;
     if (n_edges < 0 || n_edges > 3 * nf)
         return nksr_set_error(NKSR_ERR_ARG, "geom edge weights: n_edges=%lld of %lld faces", (long long)n_edges, (long long)nf);
     if (n_edges == 0) return NKSR_OK;
     if (!ids_sorted || !edge_start || !cot || !weight_out) return nksr_set_error(NKSR_ERR_ARG, "geom edge weights: NULL arrays");
-    GM_LAUNCH(k_geom_edge_weights, n_edges, (hipStream_t)stream, ids_sorted, edge_start, n_edges, cot, weight_out);
+    MESH_LAUNCH(k_geom_edge_weights, n_edges, (hipStream_t)stream, ids_sorted, edge_start, n_edges, cot, weight_out);
     return NKSR_OK;
 }
 
 extern "C" int nksr_geom_vertex_gather(const uint32_t* corner_start, const uint32_t* corner_ids, int64_t nv, int64_t nf, const double* angle,
                                        const double* face_normal, const double* face_area, int weighting, double* normal_out, double* area_out,
                                        double* angle_sum_out, void* stream) {
-    int rc = gm_check_mesh("geom vertex gather", nv, nf);
+    int rc = mesh_check_sizes("geom vertex gather", nv, nf);
     if (rc) return rc;
     if (weighting != NKSR_GEOM_WEIGHT_ANGLE && weighting != NKSR_GEOM_WEIGHT_AREA)
         return nksr_set_error(NKSR_ERR_ARG, "geom vertex gather: weighting=%d is neither angle (0) nor area (1)", weighting);
     if (nv == 0) return NKSR_OK;
     if (!corner_start || (nf > 0 && (!corner_ids || !angle || !face_normal || !face_area)) || (!normal_out && !area_out && !angle_sum_out))
         return nksr_set_error(NKSR_ERR_ARG, "geom vertex gather: NULL arrays");
-    GM_LAUNCH(k_geom_vertex_gather, nv, (hipStream_t)stream, corner_start, corner_ids, nv, angle, face_normal, face_area, weighting, normal_out,
+    MESH_LAUNCH(k_geom_vertex_gather, nv, (hipStream_t)stream, corner_start, corner_ids, nv, angle, face_normal, face_area, weighting, normal_out,
               area_out, angle_sum_out);
     return NKSR_OK;
 }
@@ -336,7 +323,7 @@ extern "C" int nksr_geom_curvature(const void* v, int v_float64, int64_t nv, con
     if (!v || !start || !vertex_area || !vertex_kind || (n_edges > 0 && (!neighbour || !neighbour_edge || !edge_weight)) ||
         (!laplacian_out && !mean_curvature_out) || (mean_curvature_out && !vertex_normal))
         return nksr_set_error(NKSR_ERR_ARG, "geom curvature: NULL arrays");
-    GM_LAUNCH(k_geom_curvature, nv, (hipStream_t)stream, v, v_float64, nv, start, neighbour, neighbour_edge, edge_weight, vertex_area, vertex_normal,
+    MESH_LAUNCH(k_geom_curvature, nv, (hipStream_t)stream, v, v_float64, nv, start, neighbour, neighbour_edge, edge_weight, vertex_area, vertex_normal,
               vertex_kind, laplacian_out, mean_curvature_out);
     return NKSR_OK;
 }
@@ -355,7 +342,7 @@ extern "C" int nksr_geom_smooth(double* x_a, double* x_b, int64_t nv, const uint
     if (x_a == x_b) return nksr_set_error(NKSR_ERR_ARG, "geom smooth: x_a and x_b are the same buffer");
     hipStream_t st = (hipStream_t)stream;
     for (int64_t s = 0; s < n_steps; ++s)           // no host synchronisation: the steps queue up behind one another
-        GM_LAUNCH(k_geom_smooth_step, nv, st, s & 1 ? x_b : x_a, s & 1 ? x_a : x_b, nv, start, neighbour, neighbour_class, vertex_kind, fixed,
+        MESH_LAUNCH(k_geom_smooth_step, nv, st, s & 1 ? x_b : x_a, s & 1 ? x_a : x_b, nv, start, neighbour, neighbour_class, vertex_kind, fixed,
                   boundary, s & 1 ? w_odd : w_even);
     return NKSR_OK;
 }

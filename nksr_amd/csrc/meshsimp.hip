@@ -2,9 +2,8 @@
 // include/nksr_hip.h, definitions in DESIGN.md section 3.14):
 //   k_simp_cell_keys        (cell key, vertex id) of every vertex: i = floor((double(x) - origin) / cell), an fp64 subtraction and an
 //                           fp64 DIVISION (never a product with a reciprocal); unreferenced vertices behind the all-ones key
-//   k_simp_run_heads        1 at the first sorted position of every distinct key
-//   k_simp_clusters         cluster id of every vertex, run start and key of every cluster
-//   k_simp_face_remap       cluster triple, valid / surviving flags and the two dedup sort keys of every face
+//   (the clusters are the runs of the sorted keys: nksr_run_counts_u64 / nksr_run_table_u64 of csrc/prims.hip)
+//   k_simp_face_remap      cluster triple, valid / surviving flags and the two dedup sort keys of every face
 //   k_simp_flag_duplicates  after the two stable sorts: a surviving face equal to its predecessor is a duplicate
 //   k_simp_place            THE HOT KERNEL: one 16-lane group per cluster sums the quadric of the cluster's corner row, lane 0 solves
 //   k_simp_cluster_means    fp64 mean of a [V, C] attribute over every cluster's vertex run
@@ -13,23 +12,16 @@
 // of its sorted run and the 16 partial sums of a group meet in a fixed xor butterfly, so every result repeats bit for bit.
 #include "common.h"
 #include "mesh_dev.h"
+#include "wave_dev.h"
 
-#define SIMP_BLOCK 256
 #define SIMP_KEY_NONE 0xFFFFFFFFFFFFFFFFull
 #define SIMP_INDEX_MASK ((1ull << 21) - 1ull)
 
-// the lanes' 0 / 1 flags become one integer atomic per wavefront
-__device__ __forceinline__ void sm_count(bool flag, int64_t* total) {
-    const unsigned long long m = __ballot(flag);
-    if (m && (threadIdx.x & (NKSR_WAVE - 1)) == (unsigned)(__ffsll((long long)m) - 1))
-        atomicAdd((unsigned long long*)total, (unsigned long long)__popcll(m));
-}
-
 // ---- 1. cell keys ----------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(SIMP_BLOCK) k_simp_cell_keys(const void* v, int v_f64, int64_t nv, const int32_t* __restrict__ vertex_ref, double ox,
+__global__ void __launch_bounds__(MESH_BLOCK) k_simp_cell_keys(const void* v, int v_f64, int64_t nv, const int32_t* __restrict__ vertex_ref, double ox,
                                                                double oy, double oz, double cell, uint64_t* __restrict__ keys,
                                                                uint32_t* __restrict__ ids, int64_t* __restrict__ misfits) {
-    const int64_t i = (int64_t)blockIdx.x * SIMP_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     bool misfit = false;
     if (i < nv) {
         uint64_t key = SIMP_KEY_NONE;
@@ -43,39 +35,15 @@ __global__ void __launch_bounds__(SIMP_BLOCK) k_simp_cell_keys(const void* v, in
         keys[i] = key;
         ids[i] = (uint32_t)i;
     }
-    sm_count(misfit, misfits);
+    wave_count(misfit, misfits);
 }
 
-// ---- 2. clusters -----------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(SIMP_BLOCK) k_simp_run_heads(const uint64_t* __restrict__ keys, int64_t nv, int32_t* __restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * SIMP_BLOCK + threadIdx.x;
-    if (i > nv) return;
-    flags[i] = (i < nv && keys[i] != SIMP_KEY_NONE && (i == 0 || keys[i - 1] != keys[i])) ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(SIMP_BLOCK) k_simp_clusters(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ ids, int64_t nv,
-                                                              const int32_t* __restrict__ flags, const int32_t* __restrict__ offsets, int64_t nk,
-                                                              int32_t* __restrict__ cluster_of, uint32_t* __restrict__ start,
-                                                              uint64_t* __restrict__ cluster_key) {
-    const int64_t i = (int64_t)blockIdx.x * SIMP_BLOCK + threadIdx.x;
-    if (i >= nv) return;
-    const uint64_t key = keys[i];
-    const int64_t vid = ids[i];
-    if (vid >= nv) return;
-    if (key == SIMP_KEY_NONE) { cluster_of[vid] = -1; return; }
-    const int64_t c = (int64_t)offsets[i] + flags[i] - 1;          // the heads up to and including this position, minus one
-    if (c < 0 || c >= nk) return;
-    cluster_of[vid] = (int32_t)c;
-    if (flags[i]) { start[c] = (uint32_t)i; cluster_key[c] = key; }
-    if (i == nv - 1 || keys[i + 1] == SIMP_KEY_NONE) start[nk] = (uint32_t)(i + 1);       // the end of the last run
-}
-
-// ---- 3. faces --------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(SIMP_BLOCK) k_simp_face_remap(const void* faces, int is64, int64_t nf, int64_t nv, const int32_t* __restrict__ cluster_of,
+// ---- 2. faces --------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(MESH_BLOCK) k_simp_face_remap(const void* faces, int is64, int64_t nf, int64_t nv, const int32_t* __restrict__ cluster_of,
                                                                 void* cluster_faces, uint8_t* __restrict__ valid, uint8_t* __restrict__ survives,
                                                                 uint64_t* __restrict__ key_ab, uint64_t* __restrict__ key_c, uint32_t* __restrict__ ids,
                                                                 int64_t* __restrict__ counts) {
-    const int64_t j = (int64_t)blockIdx.x * SIMP_BLOCK + threadIdx.x;
+    const int64_t j = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     bool ok = false, collapsed = false;
     if (j < nf) {
         int64_t c[3];
@@ -102,14 +70,14 @@ __global__ void __launch_bounds__(SIMP_BLOCK) k_simp_face_remap(const void* face
         key_c[j] = alive ? (uint64_t)hi : 0ull;
         ids[j] = (uint32_t)j;
     }
-    sm_count(j < nf && !ok, counts);
-    sm_count(collapsed, counts + 1);
+    wave_count(j < nf && !ok, counts);
+    wave_count(collapsed, counts + 1);
 }
 
-__global__ void __launch_bounds__(SIMP_BLOCK) k_simp_flag_duplicates(const uint32_t* __restrict__ order, int64_t nf, const uint64_t* __restrict__ key_ab,
+__global__ void __launch_bounds__(MESH_BLOCK) k_simp_flag_duplicates(const uint32_t* __restrict__ order, int64_t nf, const uint64_t* __restrict__ key_ab,
                                                                      const uint64_t* __restrict__ key_c, const uint8_t* __restrict__ survives,
                                                                      uint8_t* __restrict__ keep, int64_t* __restrict__ count) {
-    const int64_t i = (int64_t)blockIdx.x * SIMP_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     bool dup = false;
     if (i < nf) {
         const int64_t p = order[i];
@@ -122,10 +90,10 @@ __global__ void __launch_bounds__(SIMP_BLOCK) k_simp_flag_duplicates(const uint3
             keep[p] = alive && !dup ? 1 : 0;
         }
     }
-    sm_count(dup, count);
+    wave_count(dup, count);
 }
 
-// ---- 4. the hot kernel: cluster quadrics and placement ---------------------------------------------------------------------------
+// ---- 3. the hot kernel: cluster quadrics and placement ---------------------------------------------------------------------------
 // centre of the cell of a key; the product and the sum are rounded one after the other, as the restatement rounds them
 __device__ __forceinline__ gm_vec3 sm_centre(uint64_t key, double ox, double oy, double oz, double cell) {
 #pragma clang fp contract(off)
@@ -146,12 +114,12 @@ __device__ __forceinline__ double sm_clamp(double x, double h) { return x < -h ?
 // positions), its normal and area recomputed, and a nn^T (6 distinct entries) and a d n (3) go into 9 fp64 accumulators.  A row of n
 // corners costs ceil(n / 16) trips.  Lane 0 then sums the cluster's vertex run for the mean, solves the regularised 3 x 3 system by
 // Cholesky, clamps to the cell and writes.  Every group of a wavefront runs the butterfly, whether its cluster exists or not.
-__global__ void __launch_bounds__(SIMP_BLOCK) k_simp_place(const void* v, int v_f64, int64_t nv, const void* faces, int is64, int64_t nf,
+__global__ void __launch_bounds__(MESH_BLOCK) k_simp_place(const void* v, int v_f64, int64_t nv, const void* faces, int is64, int64_t nf,
                                                            const uint32_t* __restrict__ corner_start, const uint32_t* __restrict__ corner_ids,
                                                            const uint32_t* __restrict__ cluster_start, const uint32_t* __restrict__ vertex_ids,
                                                            const uint64_t* __restrict__ cluster_key, int64_t nk, double ox, double oy, double oz,
                                                            double cell, double mu, int placement, double* __restrict__ out) {
-    const int64_t g = ((int64_t)blockIdx.x * SIMP_BLOCK + threadIdx.x) / NKSR_SIMP_GROUP;
+    const int64_t g = ((int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x) / NKSR_SIMP_GROUP;
     const int lane = threadIdx.x & (NKSR_SIMP_GROUP - 1);
     const bool on = g < nk;
     const gm_vec3 centre = on ? sm_centre(cluster_key[g], ox, oy, oz, cell) : gm_vec3{0.0, 0.0, 0.0};
@@ -221,11 +189,11 @@ __global__ void __launch_bounds__(SIMP_BLOCK) k_simp_place(const void* v, int v_
     out[g * 3 + 2] = centre.z + sm_clamp(x.z, h);
 }
 
-// ---- 5. attribute means ----------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(SIMP_BLOCK) k_simp_cluster_means(const void* attr, int attr_f64, int64_t nv, int64_t nc,
+// ---- 4. attribute means ----------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(MESH_BLOCK) k_simp_cluster_means(const void* attr, int attr_f64, int64_t nv, int64_t nc,
                                                                    const uint32_t* __restrict__ cluster_start, const uint32_t* __restrict__ vertex_ids,
                                                                    int64_t nk, double* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * SIMP_BLOCK + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (i >= nk * nc) return;
     const int64_t g = i / nc, ch = i - g * nc;
     const int64_t v0 = cluster_start[g], v1 = cluster_start[g + 1];
@@ -239,12 +207,6 @@ __global__ void __launch_bounds__(SIMP_BLOCK) k_simp_cluster_means(const void* a
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------
-static int sm_check_mesh(const char* who, int64_t nv, int64_t nf) {
-    if (nv < 0 || nf < 0) return nksr_set_error(NKSR_ERR_ARG, "%s: negative size (nv=%lld, nf=%lld)", who, (long long)nv, (long long)nf);
-    if (nv >= (1ll << 31)) return nksr_set_error(NKSR_ERR_ARG, "%s: nv=%lld, at most 2^31 - 1 vertices", who, (long long)nv);
-    if (nf > NKSR_TOPO_MAX_FACES) return nksr_set_error(NKSR_ERR_ARG, "%s: %lld faces > 2^30", who, (long long)nf);
-    return NKSR_OK;
-}
 static int sm_check_clusters(const char* who, int64_t nk, int64_t nv) {
     if (nk < 0 || nk > nv) return nksr_set_error(NKSR_ERR_ARG, "%s: n_clusters=%lld of %lld vertices", who, (long long)nk, (long long)nv);
     return NKSR_OK;
@@ -256,49 +218,23 @@ static int sm_check_grid(const char* who, const double* origin, double cell) {
         if (origin[k] - origin[k] != 0.0) return nksr_set_error(NKSR_ERR_ARG, "%s: non-finite origin", who);
     return NKSR_OK;
 }
-#define SM_LAUNCH(kernel, n, st, ...)                                                                                      \
-    do {                                                                                                                   \
-        hipLaunchKernelGGL(kernel, dim3(nksr_blocks((n), SIMP_BLOCK)), dim3(SIMP_BLOCK), 0, (st), __VA_ARGS__);             \
-        NKSR_CHECK_LAUNCH();                                                                                               \
-    } while (0)
 
 extern "C" int nksr_simp_cell_keys(const void* v, int v_float64, int64_t nv, const int32_t* vertex_ref, const double* origin, double cell_size,
                                    uint64_t* keys_out, uint32_t* ids_out, int64_t* misfits_out, void* stream) {
-    int rc = sm_check_mesh("simp cell keys", nv, 0);
+    int rc = mesh_check_sizes("simp cell keys", nv, 0);
     if (rc) return rc;
     if ((rc = sm_check_grid("simp cell keys", origin, cell_size))) return rc;
     if (!misfits_out || (nv > 0 && (!v || !vertex_ref || !keys_out || !ids_out))) return nksr_set_error(NKSR_ERR_ARG, "simp cell keys: NULL arrays");
     hipStream_t st = (hipStream_t)stream;
     NKSR_CHECK_HIP(hipMemsetAsync(misfits_out, 0, sizeof(int64_t), st));
-    if (nv > 0) SM_LAUNCH(k_simp_cell_keys, nv, st, v, v_float64, nv, vertex_ref, origin[0], origin[1], origin[2], cell_size, keys_out, ids_out, misfits_out);
-    return NKSR_OK;
-}
-
-extern "C" int nksr_simp_run_heads(const uint64_t* keys_sorted, int64_t nv, int32_t* flags_out, void* stream) {
-    int rc = sm_check_mesh("simp run heads", nv, 0);
-    if (rc) return rc;
-    if (!flags_out || (nv > 0 && !keys_sorted)) return nksr_set_error(NKSR_ERR_ARG, "simp run heads: NULL arrays");
-    SM_LAUNCH(k_simp_run_heads, nv + 1, (hipStream_t)stream, keys_sorted, nv, flags_out);
-    return NKSR_OK;
-}
-
-extern "C" int nksr_simp_clusters(const uint64_t* keys_sorted, const uint32_t* ids_sorted, int64_t nv, const int32_t* flags, const int32_t* offsets,
-                                  int64_t n_clusters, int32_t* cluster_of_out, uint32_t* cluster_start_out, uint64_t* cluster_key_out, void* stream) {
-    int rc = sm_check_mesh("simp clusters", nv, 0);
-    if (rc) return rc;
-    if ((rc = sm_check_clusters("simp clusters", n_clusters, nv))) return rc;
-    if (!cluster_start_out || (nv > 0 && (!keys_sorted || !ids_sorted || !flags || !offsets || !cluster_of_out)) || (n_clusters > 0 && !cluster_key_out))
-        return nksr_set_error(NKSR_ERR_ARG, "simp clusters: NULL arrays");
-    hipStream_t st = (hipStream_t)stream;
-    NKSR_CHECK_HIP(hipMemsetAsync(cluster_start_out, 0, sizeof(uint32_t) * (size_t)(n_clusters + 1), st));
-    if (nv > 0) SM_LAUNCH(k_simp_clusters, nv, st, keys_sorted, ids_sorted, nv, flags, offsets, n_clusters, cluster_of_out, cluster_start_out, cluster_key_out);
+    if (nv > 0) MESH_LAUNCH(k_simp_cell_keys, nv, st, v, v_float64, nv, vertex_ref, origin[0], origin[1], origin[2], cell_size, keys_out, ids_out, misfits_out);
     return NKSR_OK;
 }
 
 extern "C" int nksr_simp_face_remap(const void* faces, int faces_int64, int64_t nf, int64_t nv, const int32_t* cluster_of, void* cluster_faces_out,
                                     uint8_t* valid_out, uint8_t* survives_out, uint64_t* key_ab_out, uint64_t* key_c_out, uint32_t* ids_out,
                                     int64_t* counts_out, void* stream) {
-    int rc = sm_check_mesh("simp face remap", nv, nf);
+    int rc = mesh_check_sizes("simp face remap", nv, nf);
     if (rc) return rc;
     if (!counts_out || (nf > 0 && (!faces || !cluster_faces_out || !valid_out || !survives_out || !key_ab_out || !key_c_out || !ids_out)) ||
         (nf > 0 && nv > 0 && !cluster_of))
@@ -306,19 +242,19 @@ extern "C" int nksr_simp_face_remap(const void* faces, int faces_int64, int64_t 
     hipStream_t st = (hipStream_t)stream;
     NKSR_CHECK_HIP(hipMemsetAsync(counts_out, 0, 2 * sizeof(int64_t), st));
     if (nf > 0)
-        SM_LAUNCH(k_simp_face_remap, nf, st, faces, faces_int64, nf, nv, cluster_of, cluster_faces_out, valid_out, survives_out, key_ab_out, key_c_out,
+        MESH_LAUNCH(k_simp_face_remap, nf, st, faces, faces_int64, nf, nv, cluster_of, cluster_faces_out, valid_out, survives_out, key_ab_out, key_c_out,
                   ids_out, counts_out);
     return NKSR_OK;
 }
 
 extern "C" int nksr_simp_flag_duplicates(const uint32_t* order, int64_t nf, const uint64_t* key_ab, const uint64_t* key_c, const uint8_t* survives,
                                          uint8_t* keep_out, int64_t* count_out, void* stream) {
-    int rc = sm_check_mesh("simp flag duplicates", 0, nf);
+    int rc = mesh_check_sizes("simp flag duplicates", 0, nf);
     if (rc) return rc;
     if (!count_out || (nf > 0 && (!order || !key_ab || !key_c || !survives || !keep_out))) return nksr_set_error(NKSR_ERR_ARG, "simp flag duplicates: NULL arrays");
     hipStream_t st = (hipStream_t)stream;
     NKSR_CHECK_HIP(hipMemsetAsync(count_out, 0, sizeof(int64_t), st));
-    if (nf > 0) SM_LAUNCH(k_simp_flag_duplicates, nf, st, order, nf, key_ab, key_c, survives, keep_out, count_out);
+    if (nf > 0) MESH_LAUNCH(k_simp_flag_duplicates, nf, st, order, nf, key_ab, key_c, survives, keep_out, count_out);
     return NKSR_OK;
 }
 
@@ -326,7 +262,7 @@ extern "C" int nksr_simp_place(const void* v, int v_float64, int64_t nv, const v
                                const uint32_t* corner_ids, const uint32_t* cluster_start, const uint32_t* vertex_ids_sorted, const uint64_t* cluster_key,
                                int64_t n_clusters, const double* origin, double cell_size, double regularisation, int placement,
                                double* representative_out, void* stream) {
-    int rc = sm_check_mesh("simp place", nv, nf);
+    int rc = mesh_check_sizes("simp place", nv, nf);
     if (rc) return rc;
     if ((rc = sm_check_clusters("simp place", n_clusters, nv))) return rc;
     if ((rc = sm_check_grid("simp place", origin, cell_size))) return rc;
@@ -338,7 +274,7 @@ extern "C" int nksr_simp_place(const void* v, int v_float64, int64_t nv, const v
     if (!v || !cluster_start || !vertex_ids_sorted || !cluster_key || !representative_out ||
         (placement == NKSR_SIMP_QUADRIC && (!faces || !corner_start || !corner_ids)))
         return nksr_set_error(NKSR_ERR_ARG, "simp place: NULL arrays");
-    SM_LAUNCH(k_simp_place, n_clusters * NKSR_SIMP_GROUP, (hipStream_t)stream, v, v_float64, nv, faces, faces_int64, nf, corner_start, corner_ids,
+    MESH_LAUNCH(k_simp_place, n_clusters * NKSR_SIMP_GROUP, (hipStream_t)stream, v, v_float64, nv, faces, faces_int64, nf, corner_start, corner_ids,
               cluster_start, vertex_ids_sorted, cluster_key, n_clusters, origin[0], origin[1], origin[2], cell_size, regularisation, placement,
               representative_out);
     return NKSR_OK;
@@ -346,7 +282,7 @@ extern "C" int nksr_simp_place(const void* v, int v_float64, int64_t nv, const v
 
 extern "C" int nksr_simp_cluster_means(const void* attr, int attr_float64, int64_t nv, int64_t channels, const uint32_t* cluster_start,
                                        const uint32_t* vertex_ids_sorted, int64_t n_clusters, double* mean_out, void* stream) {
-    int rc = sm_check_mesh("simp cluster means", nv, 0);
+    int rc = mesh_check_sizes("simp cluster means", nv, 0);
     if (rc) return rc;
     if ((rc = sm_check_clusters("simp cluster means", n_clusters, nv))) return rc;
     if (channels < 0 || channels > (1 << 16)) return nksr_set_error(NKSR_ERR_ARG, "simp cluster means: channels=%lld outside [0, 65536]", (long long)channels);
@@ -354,7 +290,7 @@ extern "C" int nksr_simp_cluster_means(const void* attr, int attr_float64, int64
         return nksr_set_error(NKSR_ERR_ARG, "simp cluster means: %lld clusters x %lld channels >= 2^38 entries", (long long)n_clusters, (long long)channels);
     if (n_clusters == 0 || channels == 0) return NKSR_OK;
     if (!attr || !cluster_start || !vertex_ids_sorted || !mean_out) return nksr_set_error(NKSR_ERR_ARG, "simp cluster means: NULL arrays");
-    SM_LAUNCH(k_simp_cluster_means, n_clusters * channels, (hipStream_t)stream, attr, attr_float64, nv, channels, cluster_start, vertex_ids_sorted,
+    MESH_LAUNCH(k_simp_cluster_means, n_clusters * channels, (hipStream_t)stream, attr, attr_float64, nv, channels, cluster_start, vertex_ids_sorted,
               n_clusters, mean_out);
     return NKSR_OK;
 }

@@ -10,6 +10,7 @@
 // Every atomic is an integer minimum, maximum or count, so nothing depends on the order the lanes ran in.  One lane per point;
 // the kernels are bound by gathers (rep[j], normal[j]) and, without the per-wavefront reduction, by same-address atomics.
 #include "common.h"
+#include "wave_dev.h"
 
 #define OR_BLOCK 256
 #define OR_MAX_GROUPS 4            // distinct representatives a wavefront reduces together; lanes beyond them go one by one
@@ -22,11 +23,6 @@ __device__ __forceinline__ float or_dot(float a0, float a1, float a2, float b0, 
 __device__ __forceinline__ uint32_t or_weight_bits(float dot) {
     const float w = fmaxf(__fsub_rn(1.0f, fabsf(dot)), 0.0f);
     return __float_as_uint(w) & 0x7FFFFFFFu;            // (max(-0, 0) may keep the sign bit: the weight 0 has one bit pattern)
-}
-// a float as an unsigned integer of the same order (-0 counted as +0)
-__device__ __forceinline__ uint32_t or_ordered(float x) {
-    const uint32_t b = __float_as_uint(x == 0.0f ? 0.0f : x);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
 __device__ __forceinline__ uint64_t or_load(const uint64_t* p) {
@@ -51,10 +47,6 @@ __device__ __forceinline__ uint64_t or_wave_max(uint64_t v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) { const uint64_t o = or_shfl_xor(v, m); v = o > v ? o : v; }
     return v;
-}
-__device__ __forceinline__ void or_count(bool flag, int32_t* total) {
-    const unsigned long long m = __ballot(flag);
-    if (m && (threadIdx.x & (NKSR_WAVE - 1)) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(total, (int32_t)__popcll(m));
 }
 // The active lanes of a wavefront grouped by label: grouped(l0, mine, leader) runs in EVERY lane once per distinct label (the first
 // OR_MAX_GROUPS of them, in the order of their first lane), single() in every active lane that is left.  In Morton order a wavefront
@@ -109,7 +101,7 @@ __global__ void __launch_bounds__(OR_BLOCK) k_orient_propose(const float* __rest
         }
         if (own == OR_NONE) done[i] = 1;                // every neighbour shares the component, and components only grow
     }
-    or_count(active, counters + 1);
+    wave_count(active, counters + 1);
     or_label_groups(ri, own != OR_NONE,
                     [&](int32_t l0, bool mine, bool leader) {
                         const uint64_t m = or_wave_min(mine ? own : OR_NONE);
@@ -146,7 +138,7 @@ __global__ void __launch_bounds__(OR_BLOCK) k_orient_hook(const float* __restric
         link[i] = to;
         lpar[i] = p;
     }
-    or_count(hooked, counters);
+    wave_count(hooked, counters);
 }
 
 __global__ void __launch_bounds__(OR_BLOCK) k_orient_jump(const int32_t* __restrict__ rep, int64_t n, const int32_t* __restrict__ link_in,
@@ -192,7 +184,7 @@ __global__ void __launch_bounds__(OR_BLOCK) k_orient_seeds(const float* __restri
             or_view(xyz, i, vx, vy, vz, t);
             hi = 0xFFFFFFFFu - __float_as_uint(or_dot(t[0], t[1], t[2], t[0], t[1], t[2]));       // nearest first
         } else {
-            hi = or_ordered(xyz[i * 3 + 2]);
+            hi = ordered_bits(xyz[i * 3 + 2]);
         }
         key = ((uint64_t)hi << 32) | (uint64_t)(~(uint32_t)i);
     }

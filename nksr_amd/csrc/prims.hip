@@ -60,6 +60,100 @@ extern "C" int nksr_exclusive_sum_i64(void* tmp, size_t* tmp_bytes, const int64_
     return NKSR_OK;
 }
 
+// ---- the run table of sorted keys (edges of a mesh, clusters of a simplification, voxels of a cloud) -----------------------------
+// Position i HEADS a run when keys[i] < none_from and (i == 0 or keys[i - 1] != keys[i]); keys >= none_from (sorted: a tail) belong to
+// no run.  Two passes of one lane per position around a scan of RUN_BLOCK-sized block counts: a ballot per wavefront, LDS only for the
+// per-wave counts.
+#define RUN_BLOCK 256
+
+// heads of the block up to this lane's wavefront in s[], returns whether this lane's position is a head; every lane must call it
+__device__ __forceinline__ bool run_head(const uint64_t* __restrict__ keys, int64_t i, int64_t n, uint64_t none_from, unsigned long long& wave_heads,
+                                         int* s) {
+    bool head = false;
+    if (i < n) {
+        const uint64_t k = keys[i];
+        head = k < none_from && (i == 0 || keys[i - 1] != k);
+    }
+    wave_heads = __ballot(head);
+    if ((threadIdx.x & (NKSR_WAVE - 1)) == 0) s[threadIdx.x / NKSR_WAVE] = __popcll(wave_heads);
+    __syncthreads();
+    return head;
+}
+
+__global__ void __launch_bounds__(RUN_BLOCK) k_run_counts(const uint64_t* __restrict__ keys, int64_t n, uint64_t none_from,
+                                                          int64_t* __restrict__ counts, int64_t nb) {
+    __shared__ int s[RUN_BLOCK / NKSR_WAVE];
+    unsigned long long m;
+    run_head(keys, (int64_t)blockIdx.x * RUN_BLOCK + threadIdx.x, n, none_from, m, s);
+    if (threadIdx.x == 0) {
+        int t = 0;
+#pragma unroll
+        for (int w = 0; w < RUN_BLOCK / NKSR_WAVE; ++w) t += s[w];
+        counts[blockIdx.x] = t;
+        if (blockIdx.x == 0) counts[nb] = 0;
+    }
+}
+
+// run r = rank of its head: start[r] = the head's position, run_key[r] its key; start[n_runs] = the position of the first key >=
+// none_from, or n; run_of[i] = the heads up to and including i, minus one (-1 behind none_from)
+__global__ void __launch_bounds__(RUN_BLOCK) k_run_table(const uint64_t* __restrict__ keys, int64_t n, uint64_t none_from,
+                                                         const int64_t* __restrict__ offsets, int64_t n_runs, uint32_t* __restrict__ start,
+                                                         uint64_t* __restrict__ run_key, int32_t* __restrict__ run_of) {
+    __shared__ int s[RUN_BLOCK / NKSR_WAVE];
+    const int64_t i = (int64_t)blockIdx.x * RUN_BLOCK + threadIdx.x;
+    unsigned long long m;
+    const bool head = run_head(keys, i, n, none_from, m, s);
+    if (i >= n) return;
+    const int lane = threadIdx.x & (NKSR_WAVE - 1), wave = threadIdx.x / NKSR_WAVE;
+    int upto = __popcll(m & ((2ull << lane) - 1ull));               // heads of this wavefront up to and including this lane
+    for (int w = 0; w < wave; ++w) upto += s[w];
+    const int64_t r = offsets[blockIdx.x] + upto - 1;
+    const uint64_t k = keys[i];
+    const bool in_run = k < none_from && r >= 0 && r < n_runs;      // (r outside [0, n_runs): offsets that are not the scan of these keys)
+    if (head && in_run) {
+        start[r] = (uint32_t)i;
+        if (run_key) run_key[r] = k;
+    }
+    if (run_of) run_of[i] = in_run ? (int32_t)r : -1;
+    if (k >= none_from ? (i == 0 || keys[i - 1] < none_from) : i == n - 1) start[n_runs] = (uint32_t)(k >= none_from ? i : n);
+}
+
+static int run_check(const char* who, int64_t n) {
+    if (n < 0) return nksr_set_error(NKSR_ERR_ARG, "%s: negative size (n=%lld)", who, (long long)n);
+    if (n >= (1ll << 32)) return nksr_set_error(NKSR_ERR_ARG, "%s: n=%lld, at most 2^32 - 1 keys (run starts are uint32)", who, (long long)n);
+    return NKSR_OK;
+}
+
+extern "C" int64_t nksr_run_blocks(int64_t n) { return n > 0 ? (n + RUN_BLOCK - 1) / RUN_BLOCK : 0; }
+
+extern "C" int nksr_run_counts_u64(const uint64_t* keys_sorted, int64_t n, uint64_t none_from, int64_t* block_counts, void* stream) {
+    int rc = run_check("run counts", n);
+    if (rc) return rc;
+    if (!block_counts || (n > 0 && !keys_sorted)) return nksr_set_error(NKSR_ERR_ARG, "run counts: NULL arrays");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) { NKSR_CHECK_HIP(hipMemsetAsync(block_counts, 0, sizeof(int64_t), st)); return NKSR_OK; }
+    const int64_t nb = nksr_run_blocks(n);
+    hipLaunchKernelGGL(k_run_counts, dim3((unsigned)nb), dim3(RUN_BLOCK), 0, st, keys_sorted, n, none_from, block_counts, nb);
+    NKSR_CHECK_LAUNCH();
+    return NKSR_OK;
+}
+
+extern "C" int nksr_run_table_u64(const uint64_t* keys_sorted, int64_t n, uint64_t none_from, const int64_t* block_offsets, int64_t n_runs,
+                                  uint32_t* start_out, uint64_t* run_key_out, int32_t* run_of_out, void* stream) {
+    int rc = run_check("run table", n);
+    if (rc) return rc;
+    if (n_runs < 0 || n_runs > n) return nksr_set_error(NKSR_ERR_ARG, "run table: n_runs=%lld of %lld keys", (long long)n_runs, (long long)n);
+    if (run_of_out && n_runs >= (1ll << 31))
+        return nksr_set_error(NKSR_ERR_ARG, "run table: n_runs=%lld, at most 2^31 - 1 runs with run_of_out (int32)", (long long)n_runs);
+    if (!start_out || (n > 0 && (!keys_sorted || !block_offsets))) return nksr_set_error(NKSR_ERR_ARG, "run table: NULL arrays");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) { NKSR_CHECK_HIP(hipMemsetAsync(start_out, 0, sizeof(uint32_t), st)); return NKSR_OK; }
+    hipLaunchKernelGGL(k_run_table, dim3((unsigned)nksr_run_blocks(n)), dim3(RUN_BLOCK), 0, st, keys_sorted, n, none_from, block_offsets, n_runs,
+                       start_out, run_key_out, run_of_out);
+    NKSR_CHECK_LAUNCH();
+    return NKSR_OK;
+}
+
 // the sampler's area CDF: rocPRIM's deterministic look-back, so the fp64 sums (and with them every sample) repeat bit for bit
 extern "C" int nksr_inclusive_sum_f64(void* tmp, size_t* tmp_bytes, const double* in, double* out, int64_t n, void* stream) {
     if (!tmp_bytes) return nksr_set_error(NKSR_ERR_ARG, "tmp_bytes is NULL");

@@ -77,19 +77,13 @@ class Clusters:
 
 
 def clusters(keys, ids, end_bit):
-    """Stable sort over ``end_bit`` bits, run heads, exclusive sum, ids and run starts (syncs once: K)."""
-    nv, dev = keys.shape[0], keys.device
+    """Stable sort over ``end_bit`` bits, then the runs of every key but the all-ones one (``ops.sorted_runs``; syncs once: K)."""
     ks, ids_sorted = ops.sort_pairs(keys, ids, end_bit=end_bit)
-    flags = torch.empty(nv + 1, dtype=torch.int32, device=dev)
-    call('nksr_simp_run_heads', ptr(ks), nv, ptr(flags), stream())
-    offsets = ops.exclusive_sum_i32(flags)
     c = Clusters()
-    c.n = int(offsets[nv].item())
-    c.cluster_of = torch.empty(nv, dtype=torch.int32, device=dev)
-    c.start = torch.empty(c.n + 1, dtype=torch.int32, device=dev)
-    c.key = torch.empty(c.n, dtype=torch.int64, device=dev)
+    c.n, c.start, c.key, run_of = ops.sorted_runs(ks, keys=True, run_of=True)
+    c.cluster_of = torch.empty_like(run_of)
+    c.cluster_of[ids_sorted.long()] = run_of          # (a permutation of [0, V): every entry is written, unreferenced vertices with -1)
     c.vertex_ids = ids_sorted
-    call('nksr_simp_clusters', ptr(ks), ptr(ids_sorted), nv, ptr(flags), ptr(offsets), c.n, ptr(c.cluster_of), ptr(c.start), ptr(c.key), stream())
     return c
 
 

@@ -9,8 +9,8 @@ statistics, removal of small components).
     keep = c.select(min_faces=10)              # [n] bool
     v2, f2, c2, vmap = t.compact(c.face_mask(keep), colors)
 
-The edge table is the sorted list of the faces' half-edges cut into runs of equal (min, max) vertex pair (csrc/meshtopo.hip, DESIGN.md
-section 3.10); components are a union-find over (face, face) pairs round every edge ('edge', the mesh notion) or over the edges as
+The edge table is the sorted list of the faces' half-edges cut into runs of equal (min, max) vertex pair (``ops.sorted_runs``, the run
+table every sorted key list here shares; csrc/meshtopo.hip); components are a union-find over (face, face) pairs round every edge ('edge', the mesh notion) or over the edges as
 (vertex, vertex) pairs ('vertex', the graph notion).  A face with an index outside [0, V) or with two equal indices is invalid: it has
 no edges, label -1, is never kept, and is counted.  Every result repeats bit for bit: the roots of the union-find are the minimum node
 index of each component whatever order the lanes ran in, the counts are integers, and the one floating-point sum (areas) is a scan in
@@ -49,24 +49,18 @@ class EdgeTable:
 
 
 def edge_runs(f, nv, ks, ids_sorted, ref):
-    """Run heads -> scan -> edges, counts, classes, face adjacency, totals (syncs twice: E, then the totals)."""
+    """The runs of the sorted keys before the invalid faces' key -> edges, counts, classes, face adjacency, totals (syncs twice: E,
+    then the totals)."""
     nf, dev = f.shape[0], f.device
-    n_half = 3 * nf
-    nb = int(lib.nksr_topo_run_blocks(n_half))
-    counts = torch.empty(nb + 1, dtype=torch.int64, device=dev)
-    call('nksr_topo_run_counts', ptr(ks), n_half, nv, ptr(counts), stream())
-    offsets = ops.exclusive_sum_i64(counts)
-    ne = int(offsets[nb].item())
     t = EdgeTable()
+    ne, t.edge_start, edge_keys, _ = ops.sorted_runs(ks, none_from=(nv << 32) | nv, keys=True)
     t.edges = torch.empty((ne, 2), dtype=torch.int32, device=dev)
-    t.edge_start = torch.empty(ne + 1, dtype=torch.int32, device=dev)
-    call('nksr_topo_edge_table', ptr(ks), n_half, nv, ptr(offsets), ne, ptr(t.edges), ptr(t.edge_start), stream())
     t.edge_counts = torch.empty(ne, dtype=torch.int32, device=dev)
     t.edge_classes = torch.empty(ne, dtype=torch.uint8, device=dev)
     t.face_adjacency = torch.empty((nf, 3), dtype=torch.int32, device=dev)
     totals = torch.empty(TOPO_TOTALS, dtype=torch.int64, device=dev)
-    call('nksr_topo_edge_classes', ptr(f), is64(f), nf, nv, ptr(ids_sorted), ptr(t.edge_start), ne, ptr(ref), ptr(t.edge_counts),
-         ptr(t.edge_classes), ptr(t.face_adjacency), ptr(totals), stream())
+    call('nksr_topo_edge_classes', ptr(f), is64(f), nf, nv, ptr(ids_sorted), ptr(edge_keys), ptr(t.edge_start), ne, ptr(ref), ptr(t.edges),
+         ptr(t.edge_counts), ptr(t.edge_classes), ptr(t.face_adjacency), ptr(totals), stream())
     t.totals = [int(x) for x in totals.tolist()]
     return t
 

@@ -4,7 +4,7 @@ import threading
 
 import torch
 
-from ._lib import call, ptr, stream, with_tmp
+from ._lib import call, lib, ptr, stream, with_tmp
 
 
 def _bits(n):
@@ -148,6 +148,28 @@ def exclusive_sum_i64(x):
     if x.numel():
         with_tmp('nksr_exclusive_sum_i64', x.device, ptr(x), ptr(out), x.numel(), stream())
     return out
+
+
+def sorted_runs(keys_sorted, none_from=None, keys=False, run_of=False):
+    """The run table of sorted int64 keys, compared as uint64 (nksr_run_counts_u64 / nksr_run_table_u64): (n_runs, start [R + 1] int32
+    (uint32 in int32) = the position of every run's head, then the position of the first key >= ``none_from`` or n, run_keys [R] int64
+    or None, run_of [n] int32 or None = the run of every position, -1 from ``none_from`` on).  ``none_from=None``: every key counts
+    but the all-ones one.  Syncs once, to read n_runs."""
+    n, dev = keys_sorted.numel(), keys_sorted.device
+    none = 0xFFFFFFFFFFFFFFFF if none_from is None else int(none_from) & 0xFFFFFFFFFFFFFFFF
+    nr = 0
+    if n:
+        nb = int(lib.nksr_run_blocks(n))
+        counts = torch.empty(nb + 1, dtype=torch.int64, device=dev)
+        call('nksr_run_counts_u64', ptr(keys_sorted), n, none, ptr(counts), stream())
+        offsets = exclusive_sum_i64(counts)
+        nr = int(offsets[nb].item())
+    start = (torch.empty if n else torch.zeros)(nr + 1, dtype=torch.int32, device=dev)      # (n = 0: the closing entry alone, no launch)
+    run_keys = torch.empty(nr, dtype=torch.int64, device=dev) if keys else None
+    runs = torch.empty(n, dtype=torch.int32, device=dev) if run_of else None
+    if n:
+        call('nksr_run_table_u64', ptr(keys_sorted), n, none, ptr(offsets), nr, ptr(start), ptr(run_keys), ptr(runs), stream())
+    return nr, start, run_keys, runs
 
 
 def compact(flags):

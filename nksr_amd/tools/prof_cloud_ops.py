@@ -3,7 +3,7 @@
     python -m nksr_amd.tools.prof_cloud_ops [--sizes 1000000 10000000] [--voxel 0.1] [--reps 5] [--json OUT]
 
 Input: ``utils.synth_scene`` (n points, 40 x 40 x 10, normals as the attribute).  HIP events, median of --reps warm runs.
-  voxel downsampling   keys (nksr_point_keys), sort (radix sort of key / index pairs), runs (unique + nksr_site_ranges), reduce
+  voxel downsampling   keys (nksr_point_keys), sort (radix sort of key / index pairs), runs (ops.sorted_runs: the run table), reduce
                        (nksr_voxel_reduce, xyz + 3 attribute channels), and the same with the nearest-point pass.  Next to it the
                        plain-torch formulation of the same means: key -> torch.unique(return_inverse) -> index_add_ -> divide.
                        Byte model of the reduce kernel: 12 B xyz + 4 B index + 4 C B attribute per point, (12 + 4 C + 4) B per voxel.
@@ -46,11 +46,8 @@ def downsample_stages(xyz, nrm, voxel, reps):
     ks, order = ops.sort_pairs(keys, ar)
 
     def runs():
-        uk = ops.unique_sorted(ks)
-        s = torch.empty(uk.numel(), dtype=torch.int32, device=dev)
-        e = torch.empty_like(s)
-        call('nksr_site_ranges', ptr(ks), n, ptr(uk), uk.numel(), 0, ptr(s), ptr(e), stream())
-        return s, e
+        s = ops.sorted_runs(ks, keys=True)[1]
+        return s[:-1], s[1:]
     out['runs'] = _time(runs, reps)
     start, end = runs()
     nv = start.numel()

@@ -4,7 +4,7 @@
 
 Case: the configs[2] mesh of tools/prof_mesh_topology (1 M-point synth_scene, detail_level 1.0, extract_dual_mesh(mise_iter=1)),
 ~2.3 M triangles, with an fp32 [V, 3] colour, at cell sizes of 2, 4 and 8 voxels.  Stages (HIP events, median of --reps warm runs; the
-read-back of K is inside 'clusters'): cell keys, clusters (sort, run heads, scan, ids and run starts), the face remap, the duplicate
+read-back of K is inside 'clusters'): cell keys, clusters (sort, then the run table of ops.sorted_runs), the face remap, the duplicate
 pass (two sorts and the comparison), the corner incidence of the clusters (keys, sort, row starts), the placement (k_simp_place, the
 hot kernel), the colour means and the final compaction.  The byte model of the placement: per corner three position rows and the 4 B
 corner id, per cluster its two run starts (8 B) and 24 B out -- what the kernel must move at least; the three face indices of a corner

@@ -133,10 +133,11 @@ def test_simplify_c_abi_argument_errors_without_a_gpu():
     for h in (0.0, -1.0, float('inf'), float('nan')):
         assert lib.nksr_simp_cell_keys(one, 0, i64(5), one, o3, dbl(h), one, one, one, null) == E and 'cell_size' in err(), h
     assert lib.nksr_simp_cell_keys(one, 0, i64(1 << 31), one, o3, dbl(1.0), one, one, one, null) == E and '2^31' in err()
-    assert lib.nksr_simp_run_heads(null, i64(5), one, null) == E and 'NULL' in err()
-    assert lib.nksr_simp_run_heads(one, i64(-5), one, null) == E and 'negative' in err()
-    assert lib.nksr_simp_clusters(one, one, i64(5), one, one, i64(6), one, one, one, null) == E and 'n_clusters' in err()
-    assert lib.nksr_simp_clusters(one, one, i64(5), one, one, i64(2), one, null, one, null) == E and 'NULL' in err()
+    every = C.c_uint64((1 << 64) - 1)                                              # the clusters are the run table of the sorted keys
+    assert lib.nksr_run_counts_u64(null, i64(5), every, one, null) == E and 'NULL' in err()
+    assert lib.nksr_run_counts_u64(one, i64(-5), every, one, null) == E and 'negative' in err()
+    assert lib.nksr_run_table_u64(one, i64(5), every, one, i64(6), one, one, one, null) == E and 'n_runs' in err()
+    assert lib.nksr_run_table_u64(one, i64(5), every, one, i64(2), null, one, one, null) == E and 'NULL' in err()
     assert lib.nksr_simp_face_remap(null, 0, i64(5), i64(9), one, one, one, one, one, one, one, one, null) == E and 'NULL' in err()
     assert lib.nksr_simp_face_remap(one, 0, big, i64(9), one, one, one, one, one, one, one, one, null) == E and '2^30' in err()
     assert lib.nksr_simp_flag_duplicates(null, i64(5), one, one, one, one, one, null) == E and 'NULL' in err()

@@ -82,13 +82,20 @@ def test_topology_c_abi_argument_errors_without_a_gpu():
     assert lib.nksr_topo_halfedge_keys(one, 0, i64(-1), i64(9), one, one, one, one, null) == _lib.ERR_ARG and 'negative' in err()
     assert lib.nksr_topo_halfedge_keys(one, 0, big, i64(9), one, one, one, one, null) == _lib.ERR_ARG and '2^30' in err()
     assert lib.nksr_topo_halfedge_keys(one, 0, i64(1), i64(1 << 31), one, one, one, one, null) == _lib.ERR_ARG and '2^31' in err()
-    assert lib.nksr_topo_run_counts(null, i64(6), i64(9), null, null) == _lib.ERR_ARG and 'NULL' in err()
-    assert lib.nksr_topo_run_counts(one, i64(7), i64(9), one, null) == _lib.ERR_ARG and 'three times' in err()
-    assert lib.nksr_topo_run_counts(one, i64(3 * ((1 << 30) + 1)), i64(9), one, null) == _lib.ERR_ARG and '2^30' in err()
-    assert lib.nksr_topo_edge_table(one, i64(6), i64(9), one, i64(7), one, one, null) == _lib.ERR_ARG and 'n_edges' in err()
-    assert lib.nksr_topo_edge_table(null, i64(6), i64(9), null, i64(2), null, null, null) == _lib.ERR_ARG and 'NULL' in err()
-    assert lib.nksr_topo_edge_classes(null, 0, i64(2), i64(9), null, null, i64(3), null, null, null, null, null, null) == _lib.ERR_ARG and 'NULL' in err()
-    assert lib.nksr_topo_edge_classes(one, 0, big, i64(9), one, one, i64(3), one, one, one, one, one, null) == _lib.ERR_ARG and '2^30' in err()
+    u64, every = C.c_uint64, C.c_uint64((1 << 64) - 1)
+    assert lib.nksr_run_counts_u64(null, i64(6), every, null, null) == _lib.ERR_ARG and 'NULL' in err() and 'run counts' in err()
+    assert lib.nksr_run_counts_u64(one, i64(-6), every, one, null) == _lib.ERR_ARG and 'negative' in err() and 'run counts' in err()
+    assert lib.nksr_run_counts_u64(one, i64(1 << 32), every, one, null) == _lib.ERR_ARG and '2^32' in err() and 'run counts' in err()
+    assert lib.nksr_run_table_u64(one, i64(6), u64(9), one, i64(7), one, one, one, null) == _lib.ERR_ARG and 'n_runs' in err() and 'run table' in err()
+    assert lib.nksr_run_table_u64(one, i64(6), u64(9), one, i64(-1), one, one, one, null) == _lib.ERR_ARG and 'n_runs' in err()
+    assert lib.nksr_run_table_u64(null, i64(6), u64(9), null, i64(2), null, null, null, null) == _lib.ERR_ARG and 'NULL' in err() and 'run table' in err()
+    assert lib.nksr_run_table_u64(one, i64(-6), u64(9), one, i64(2), one, one, one, null) == _lib.ERR_ARG and 'negative' in err()
+    assert lib.nksr_run_table_u64(one, i64(1 << 32), u64(9), one, i64(2), one, one, one, null) == _lib.ERR_ARG and '2^32' in err()
+    assert lib.nksr_run_table_u64(one, i64((1 << 32) - 1), u64(9), one, i64(1 << 31), one, one, one, null) == _lib.ERR_ARG and '2^31' in err()
+    assert lib.nksr_topo_face_pairs(one, one, i64(7), i64(9), one, null) == _lib.ERR_ARG and 'three times' in err()
+    assert lib.nksr_topo_face_pairs(one, one, i64(3 * ((1 << 30) + 1)), i64(9), one, null) == _lib.ERR_ARG and '2^30' in err()
+    assert lib.nksr_topo_edge_classes(null, 0, i64(2), i64(9), null, null, null, i64(3), null, null, null, null, null, null, null) == _lib.ERR_ARG and 'NULL' in err()
+    assert lib.nksr_topo_edge_classes(one, 0, big, i64(9), one, one, one, i64(3), one, one, one, one, one, one, null) == _lib.ERR_ARG and '2^30' in err()
     assert lib.nksr_topo_face_pairs(null, null, i64(6), i64(9), null, null) == _lib.ERR_ARG and 'NULL' in err()
     assert lib.nksr_uf_components(null, i64(4), null, null, i64(0), null, null) == _lib.ERR_ARG and 'NULL' in err()
     assert lib.nksr_uf_components(one, i64(-4), null, one, i64(1), one, null) == _lib.ERR_ARG and 'negative' in err()
@@ -106,7 +113,7 @@ def test_topology_c_abi_argument_errors_without_a_gpu():
     nbytes = C.c_size_t(0)
     assert lib.nksr_inclusive_sum_by_key_f64(one, C.byref(nbytes), null, null, null, i64(4), null) == _lib.ERR_ARG and 'NULL' in err()
     assert lib.nksr_inclusive_sum_by_key_f64(null, None, null, null, null, i64(4), null) == _lib.ERR_ARG and 'tmp_bytes' in err()
-    assert lib.nksr_topo_run_blocks(i64(0)) == 0 and lib.nksr_topo_run_blocks(i64(257)) == 2
+    assert lib.nksr_run_blocks(i64(0)) == 0 and lib.nksr_run_blocks(i64(257)) == 2
     import pytest
     with pytest.raises(RuntimeError):
         _lib.call('nksr_topo_face_pairs', null, null, 6, 9, null, null)
