@@ -300,7 +300,7 @@ int nksr_packed_rows(int32_t n, const uint64_t* mir_sorted, const int32_t* runs,
                      const float* diag, uint32_t* packed_out, float* dis_out, void* stream);
 
 /* ---- PCG (the CG SpMV is the roofline kernel) -------------------- */
-/* nnz-chunked streaming CSR SpMV (csrc/pcg.hip).  cols/vals live in a tile-interleaved physical layout
+/* nnz-chunked streaming CSR SpMV (csrc/spmv.hip).  cols/vals live in a tile-interleaved physical layout
  * chosen by col_format (the same value must be given to nksr_assemble / nksr_place_mirrors, which
  * write it):
  *   0: 256-entry tiles, logical entry m of a tile at 4*(m%64) + m/64, int32 columns, zero-padded (valid
@@ -346,7 +346,7 @@ int nksr_pcg_profile_bytes(double* algorithmic_out, double* physical_out);
  * the CSR SpMV; 2 x 8 bytes per stored entry + 12 M + 4 for the matrix-free operator, more than it moves). */
 double nksr_pcg_profile_survey_bytes(void);
 
-/* ---- coarse-level block preconditioner of the PCG (csrc/pcg.hip) -----------------------------------------------------
+/* ---- coarse-level block preconditioner of the PCG (csrc/cheb.hip) ----------------------------------------------------
  * The unknowns of the levels >= c0 (the LAST n of the M: unknowns are level-major) take `steps` Jacobi-preconditioned
  * Chebyshev steps on their diagonal block A_cc instead of one Jacobi step; all finer unknowns keep Jacobi.  A_cc: plain CSR
  * (nksr_assemble with col_format 2 on the hierarchy whose fine levels have n = 0, hcap = 0 and whose coarse levels are

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libnksr_hip.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'nksr_hip.h')     # the C ABI: a source of the library, and what _lib.py binds from
-SOURCES = ['prims.hip', 'hierarchy.hip', 'kfield.hip', 'rows.hip', 'evalf.hip', 'assemble.hip', 'pcg.hip', 'fused.hip', 'meshing.hip', 'nn.hip', 'knn.hip', 'chunks.hip', 'metrics.hip', 'meshquery.hip', 'meshtopo.hip', 'meshgeom.hip', 'meshsimp.hip', 'cloud.hip', 'orient.hip']
+SOURCES = ['prims.hip', 'hierarchy.hip', 'kfield.hip', 'rows.hip', 'evalf.hip', 'assemble.hip', 'spmv.hip', 'cheb.hip', 'pcg.hip', 'fused.hip', 'meshing.hip', 'nn.hip', 'knn.hip', 'chunks.hip', 'metrics.hip', 'meshquery.hip', 'meshtopo.hip', 'meshgeom.hip', 'meshsimp.hip', 'cloud.hip', 'orient.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result'] + os.environ.get('NKSR_EXTRA_HIPCC_FLAGS', '').split()
 
@@ -40,7 +40,7 @@ def source_hash():
 
 
 KERNEL_SOURCES = {'fused': ['fused.hip', 'pcg_core.h', 'common.h'],      # k_fz_sweep / k_fz_gather / k_fz_cellsum
-                  'spmv': ['pcg.hip', 'pcg_core.h', 'common.h']}         # k_spmv / k_spmv_fixup
+                  'spmv': ['spmv.hip', 'spmv.h', 'common.h']}            # k_spmv / k_spmv_fixup
 
 
 def kernel_hash(kind):

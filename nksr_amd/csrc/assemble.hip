@@ -20,13 +20,13 @@
 //  4. a STABLE radix sort of that list on the destination-row bits (3 passes over HALF of the
 //     entries) orders every row's mirrors by ascending source row; k_place_mirrors drops them into
 //     the CSR.  Deterministic and exactly symmetric, no float atomics, no full COO.
-//  The coarse-level block of the PCG's preconditioner, when it is stored packed (csrc/pcg.hip, format 1), skips the CSR: steps 3 and 4
+//  The coarse-level block of the PCG's preconditioner, when it is stored packed (csrc/cheb.hip, format 1), skips the CSR: steps 3 and 4
 //  become  3'. k_row_diag (every diagonal, ahead of the fill) + the fill with the drop test inside (kept entries leave as packed words),
 //  4'. the kept mirror words alone compacted, sorted keys-only, and one kernel that writes the packed rows -- "the packed coarse block
 //  straight from the slot frame" below, nksr_assemble_packed in include/nksr_hip.h.
 #include "common.h"
+#include "coarse_pack_dev.h"
 #include <stdlib.h>
-#include <hip/hip_fp16.h>
 
 #define ASM_WAVES 1
 
@@ -50,9 +50,9 @@ __device__ __forceinline__ int row_level(const nksr_hier_t& h, int row) {
     return d;
 }
 
-// physical CSR layout (see csrc/pcg.hip): tiles of 64 EPL entries, logical entry m of a tile at
+// physical CSR layout (see csrc/spmv.hip): tiles of 64 EPL entries, logical entry m of a tile at
 // EPL (m % 64) + m / 64;  EPL = 4 (col_format 0, 256-entry tiles) or 3 (col_format 1, 192-entry tiles); col_format 2 = plain CSR
-// order (the small coarse-level block of the PCG's preconditioner, csrc/pcg.hip)
+// order (the small coarse-level block of the PCG's preconditioner, csrc/cheb.hip)
 __device__ __forceinline__ int64_t csr_phys(int64_t k, int fmt) {
     if (fmt == 2) return k;
     if (fmt == 0) {
@@ -571,7 +571,7 @@ __device__ __forceinline__ void load_cols(const float* __restrict__ row, int lan
 
 // ---- the packed coarse block straight from the slot frame (nksr_assemble_packed) ---------------------------------------------------
 // The preconditioner's block is stored Jacobi-scaled in half precision with the entries below `drop` of the unit diagonal left out
-// (csrc/pcg.hip, format 1): a row is assembled with ~250 entries and keeps ~37.  The drop test of entry (i, j) needs nothing the fill
+// (csrc/cheb.hip, format 1): a row is assembled with ~250 entries and keeps ~37.  The drop test of entry (i, j) needs nothing the fill
 // does not hold except the diagonal of row j, and that is ONE element of each of the 27 neighbour cells' blocks: k_row_diag forms all
 // diagonals ahead of the fill (same terms, same order, same bits), and the fill (PACK) emits only what survives --
 //   own entries (same-level lower, own upper) as final packed words  half << 16 | column local to the segment,  compacted inside the
@@ -581,11 +581,8 @@ __device__ __forceinline__ void load_cols(const float* __restrict__ row, int lan
 //   kept[0 / 1 / 2][row] = kept lower / upper / mirror entries.
 // The kept mirror words are then compacted to a dense list (ascending source row), sorted stably on the destination bits alone
 // (keys only, a seventh of the entries at 8 instead of 12 bytes), and k_pk_rows writes every row  [mirrors][lower][upper]  in the
-// new order: word for word what nksr_coarse_pack makes of the fp32 CSR, which is never written.
-// cc_scaled / cc_keep: the drop rule of csrc/pcg.hip (k_cc_pack), restated -- tests/test_gpu_coarse_direct.py compares the two paths
-// word for word.
-__device__ __forceinline__ __half cc_scaled(float v, float di, float dj) { return __float2half_rn(v * (di * dj)); }
-__device__ __forceinline__ bool cc_keep(__half hv, float drop) { return fabsf(__half2float(hv)) >= drop; }
+// new order: word for word what nksr_coarse_pack makes of the fp32 CSR, which is never written.  The drop rule and the 32-bit word are
+// those of coarse_pack_dev.h, which both paths include.
 
 struct AsmPackOut {
     const float* diag;          // [M] from k_row_diag
@@ -722,21 +719,20 @@ __global__ void __launch_bounds__(ASM_WAVES * 64) k_row_fill(AsmArgs A, const in
             const int cv = (t < nslots) ? cm[t] : -1;
             const bool up = cv >= 0, low = cv <= -2;
             bool keep = false;
-            uint32_t hbits = 0u;
+            __half hv = __ushort_as_half(0);
             int ncol = 0;
             if (up | low) {
                 const int col = up ? cv : -2 - cv;
-                const __half hv = cc_scaled(acc[t], di, 1.f / sqrtf(K.diag[col]));
+                hv = cc_scaled(acc[t], di, 1.f / sqrtf(K.diag[col]));
                 keep = cc_keep(hv, K.drop);
-                hbits = (uint32_t)__half_as_ushort(hv) << 16;
                 ncol = K.new_of_old[col];
             }
             const bool ku = keep && up, kl = keep && low, km = ku && t >= 125;
             const unsigned long long mu = __ballot(ku), ml = __ballot(kl), mm = __ballot(km);
             const unsigned long long below = (1ull << lane) - 1ull;
             if (keep) {
-                K.own[ku ? opos + __popcll(mu & below) : lpos + __popcll(ml & below)] = hbits | (uint32_t)(ncol - base);
-                if (km) K.mir[mpos + __popcll(mm & below)] = ((uint64_t)(uint32_t)ncol << 32) | (uint64_t)(hbits | ((uint32_t)local & 0xFFFFu));
+                K.own[ku ? opos + __popcll(mu & below) : lpos + __popcll(ml & below)] = cc_word(hv, (uint32_t)(ncol - base));
+                if (km) K.mir[mpos + __popcll(mm & below)] = ((uint64_t)(uint32_t)ncol << 32) | (uint64_t)cc_word(hv, (uint32_t)local & 0xFFFFu);
             }
             opos += __popcll(mu);
             lpos += __popcll(ml);
@@ -828,7 +824,7 @@ __global__ void __launch_bounds__(256) k_pk_lens(int n, const int32_t* __restric
 }
 
 // row i of the packed block (new order) = [kept mirrors, ascending source row][kept same-level lower][kept own upper] -- the order
-// k_cc_pack (csrc/pcg.hip) leaves of the CSR row -- and dis[i] = D^-1/2.  16 lanes per row.
+// k_cc_pack (csrc/cheb.hip) leaves of the CSR row -- and dis[i] = D^-1/2.  16 lanes per row.
 __global__ void __launch_bounds__(256) k_pk_rows(int n, const uint64_t* __restrict__ sorted, const int32_t* __restrict__ runs,
                                                  const uint32_t* __restrict__ own, const int32_t* __restrict__ own_off,
                                                  const int32_t* __restrict__ samelow, const int32_t* __restrict__ kept,

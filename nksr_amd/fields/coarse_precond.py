@@ -1,4 +1,4 @@
-"""Block preconditioner of the coarse levels of a KernelField's normal equations (nksr_coarse_precond_t, csrc/pcg.hip): the
+"""Block preconditioner of the coarse levels of a KernelField's normal equations (nksr_coarse_precond_t, csrc/cheb.hip): the
 diagonal block of the levels >= c0 as a small CSR, packed where it fits, and the Chebyshev interval of every segment's block."""
 import ctypes as C
 import os
@@ -28,7 +28,7 @@ def _renumber(n, row_seg, counts):
 
 
 def _pack_block(rowptr, cols, vals, diag, n, row_seg, counts, drop):
-    """The block in packed form (csrc/pcg.hip, format 1): rows regrouped by segment, Jacobi-scaled half-precision values + 16-bit
+    """The block in packed form (csrc/cheb.hip, format 1): rows regrouped by segment, Jacobi-scaled half-precision values + 16-bit
     segment-local columns, off-diagonal entries below ``drop`` of the unit diagonal left out."""
     dev = rowptr.device
     o2n, n2o, seg_base, row_seg_new = _renumber(n, row_seg, counts)
@@ -45,7 +45,7 @@ def _pack_block(rowptr, cols, vals, diag, n, row_seg, counts, drop):
 
 
 def coarse_precond(fld, op, reg_weight, segments=None, sites=None, override=None):
-    """Block preconditioner of the coarse levels (nksr_coarse_precond_t, csrc/pcg.hip): the diagonal block of the levels >= c0
+    """Block preconditioner of the coarse levels (nksr_coarse_precond_t, csrc/cheb.hip): the diagonal block of the levels >= c0
     assembled as a small plain CSR + the largest Jacobi-scaled eigenvalue of every segment's block (left on the device: no
     host sync).  solver_config['coarse_precond']: None = automatic (see solve_fused), False = off, or a dict
     {'first_level', 'steps', 'ratio', 'packed', 'drop', 'direct'}."""
@@ -66,7 +66,7 @@ def coarse_precond(fld, op, reg_weight, segments=None, sites=None, override=None
     nseg = segments.nseg if segments is not None else 1
     td = _tick('_', time.perf_counter())
     row_seg = segments.unknown_seg[off[c0]:].contiguous() if segments is not None else None
-    # packed form (csrc/pcg.hip, format 1): Jacobi-scaled half-precision values + 16-bit segment-local columns, 4 bytes per entry
+    # packed form (csrc/cheb.hip, format 1): Jacobi-scaled half-precision values + 16-bit segment-local columns, 4 bytes per entry
     # instead of 8 -- when every segment holds fewer than 2^16 coarse unknowns (chunks do; a large single field does not).  That
     # depends on row_seg alone: decided here, ahead of the assembly, which then emits the packed words itself (no fp32 CSR)
     rs = row_seg if row_seg is not None else torch.zeros(n, dtype=torch.int32, device=fld.device)

@@ -1,7 +1,7 @@
 """Differentiable statement of the dense-slot kernel rows in torch ops -- the TRAINING path only (SURVEY.md section 8f-4:
 ``solve_non_fused`` runs under autograd at models/nksr_net.py:105-112 and the loss back-propagates into the basis features
 and the interpolator weights).  The solve-time path never comes here: rows, operator, PCG and evaluation are HIP
-(csrc/kfield.hip, fused.hip, pcg.hip).  What this file is for: the vector-Jacobian products  sum_r g_r . dR_r/dtheta  that the
+(csrc/kfield.hip, fused.hip, spmv.hip, cheb.hip, pcg.hip).  What this file is for: the vector-Jacobian products  sum_r g_r . dR_r/dtheta  that the
 implicit-function backward of the solve and of evaluate_f need (autograd._SolveFunction / _EvaluateFunction).  They are
 taken by torch autograd through this statement of  R(theta)  (DESIGN.md section 2.3):
 

@@ -1,4 +1,4 @@
-"""CSR SpMV + Jacobi-PCG wrappers (csrc/pcg.hip).  The solve behind
+"""CSR SpMV + Jacobi-PCG wrappers (csrc/spmv.hip, csrc/pcg.hip).  The solve behind
 ``KernelField.solve*`` (reference call site models/nksr_net.py:105-112; ``solver_tol``
 examples/recons_waymo.py:33)."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""numpy restatement of the coarse-level block preconditioner (csrc/pcg.hip, k_cheb_coeffs .. cheb_apply) and the inputs its tests
+"""numpy restatement of the coarse-level block preconditioner (csrc/cheb.hip, k_cheb_coeffs .. cheb_apply) and the inputs its tests
 share.  Imports nothing of nksr_amd.
 
 The operator (include/nksr_hip.h, nksr_coarse_precond_t).  With S = D^-1/2 A D^-1/2 = U diag(lam) U^T, k = steps, the interval

@@ -149,22 +149,16 @@ def test_csr_physical_layouts_roundtrip_on_cpu():
     cols = rng.integers(0, 1 << 21, nnz).astype(np.int64)
     vals = rng.standard_normal(nnz).astype(np.float32)
     rowptr = torch.tensor([0, nnz], dtype=torch.int32)
-    k = np.arange(nnz)
+    import spmv_layout          # the encoders (tests/spmv_layout.py), shared with the GPU tests that build a CSR by hand
     # format 0: 256-entry tiles, entry m of a tile at 4 (m % 64) + m / 64, int32 columns
-    m = k & 255
-    phys = (k & ~255) + 4 * (m & 63) + (m >> 6)
-    npad = (nnz + 4095) // 4096 * 4096
-    c0, v0 = np.zeros(npad, np.int32), np.zeros(npad, np.float32)
-    c0[phys], v0[phys] = cols, vals
+    c0, v0 = spmv_layout.encode0(cols, vals)
+    assert len(c0) == 8192
     lc, lv = solver.csr_logical(rowptr, torch.from_numpy(c0), torch.from_numpy(v0))
     assert np.array_equal(lc.numpy(), cols) and np.array_equal(lv.numpy(), vals)
     # format 1: 192-entry tiles, entry m at 3 (m % 64) + m / 64, three 21-bit columns per 64-bit word
-    t, m = k // 192, k % 192
-    phys = t * 192 + 3 * (m & 63) + (m >> 6)
-    npad = (nnz + 4607) // 4608 * 4608
-    c32, v1 = np.zeros(npad, np.int64), np.zeros(npad, np.float32)
-    c32[phys], v1[phys] = cols, vals
-    packed = c32[0::3] | (c32[1::3] << 21) | (c32[2::3] << 42)
+    c32, v1 = spmv_layout.encode1(cols, vals)
+    assert len(c32) == 9216
+    packed = spmv_layout.pack21(c32)
     lc, lv = solver.csr_logical(rowptr, torch.from_numpy(packed), torch.from_numpy(v1))
     assert lc.dtype == torch.int32 and np.array_equal(lc.numpy(), cols) and np.array_equal(lv.numpy(), vals)
     assert solver.col_format(torch.from_numpy(packed)) == 1 and solver.col_format(torch.from_numpy(c0)) == 0

@@ -1,4 +1,4 @@
-"""The coarse-level block preconditioner (csrc/pcg.hip, k_cheb_coeffs .. cheb_apply, the packer, the eigenvalue bounds) against the
+"""The coarse-level block preconditioner (csrc/cheb.hip, k_cheb_coeffs .. cheb_apply, the packer, the eigenvalue bounds) against the
 fp64 references of tests/coarse_precond_ref.py, which tests/test_coarse_precond_cpu.py verifies without a GPU.
 
 The margin rule.  An fp32 evaluation of the operator cannot sit closer to the closed form than rounding allows; how close that is
@@ -17,6 +17,7 @@ import torch
 
 import coarse_precond_ref as R
 import parity_util as pu
+import spmv_layout
 
 pytestmark = pytest.mark.gpu
 
@@ -323,13 +324,7 @@ def test_first_pcg_iterate_carries_the_preconditioner(fmt, drop):
     steps = 8
     b = R.rhs(M, 8)
     # the whole matrix in the tile layout (the encoder of test_csr_physical_layouts_roundtrip_on_cpu)
-    nnz = int(full['rowptr'][-1])
-    kk = np.arange(nnz)
-    m = kk & 255
-    phys = (kk & ~255) + 4 * (m & 63) + (m >> 6)
-    npad = (nnz + 4095) // 4096 * 4096
-    c0, v0 = np.zeros(npad, np.int32), np.zeros(npad, np.float32)
-    c0[phys], v0[phys] = full['cols'], full['vals']
+    c0, v0 = spmv_layout.encode0(full['cols'], full['vals'])
     P = Precond(blk, pk, prep['lam'], steps, first=first, with_row_seg=False)
     x, iters, _ = solver.pcg_solve(_dev(full['rowptr'], np.int32), _dev(c0, np.int32), _dev(v0, np.float32), _dev(full['diag'], np.float32), _dev(b, np.float32),
                                    tol=0.0, max_iter=1, check_every=1, precond=P.pc)

@@ -792,7 +792,7 @@ def test_tree_depth_5_matches_oracle():
 
 def test_coarse_block_preconditioner_same_solution_fewer_iterations():
     """tree_depth 5 (configs[4]): the matrix-free PCG preconditions the levels >= 2 with Chebyshev steps on their diagonal block
-    (csrc/pcg.hip, nksr_coarse_precond_t).  Same system, same stopping rule: the solution agrees with the Jacobi-only solve, in
+    (csrc/cheb.hip, nksr_coarse_precond_t).  Same system, same stopping rule: the solution agrees with the Jacobi-only solve, in
     fewer iterations; the block is the corresponding block of the assembled matrix; two runs are bit-identical."""
     import scipy.sparse as sp
     import nksr_amd
