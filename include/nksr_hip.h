@@ -255,15 +255,16 @@ int nksr_assemble_count(const nksr_hier_t* h, void* workspace, int32_t* rowcount
                         int32_t* indeg, void* stream);
 /* Bytes of scratch (per-cell blocks + per-row column map) shared by nksr_assemble_count / nksr_assemble. */
 size_t nksr_assemble_workspace_bytes(const nksr_hier_t* h);
-/* Two-phase assembly of  sum_s w_s R_s^T R_s + reg I  (csrc/assemble.hip): per-cell dense blocks (fp32 MFMA),
+/* Two-phase assembly of  sum_s w_s R_s^T R_s + reg I  (csrc/gram.hip, csrc/assemble.hip): per-cell dense blocks (fp32 MFMA),
  * then one wavefront per row.  rowptr = exclusive scan of (indeg + samelow + rowcount + 1), mir_off =
  * exclusive scan of crosscount.  Same-level lower, own upper entries and the diagonal are written straight
  * into cols_out / vals_out (tile-interleaved physical layout, see nksr_spmv_csr); the mirrored copies of the
  * cross-level entries go to mir_keys (src_row << col_bits | dst_row) / mir_vals.  Also writes diag_out and
  * b = sum_s w_s R_s^T t_s.
- * split_scratch (nksr_assemble_split_bytes(h, sum_s n_s ncomp_s) bytes; NULL = off): levels whose cells hold > 1024 site rows
- * on average are accumulated by several wavefronts per cell and reduced in a fixed order. */
-size_t nksr_assemble_split_bytes(const nksr_hier_t* h, int64_t total_rows);
+ * Levels >= 3 split: the block of a cell with R site rows is the sum, in order, of min(4^(d-2), 64, R / 128) parts.  With
+ * split_scratch (nksr_assemble_split_bytes(h) bytes) a level of at most 65536 (cell, part) pairs whose tiles fit runs one wavefront
+ * per pair and reduces in that order; otherwise (or NULL) one wavefront per cell walks its parts: the same bits either way. */
+size_t nksr_assemble_split_bytes(const nksr_hier_t* h);
 int nksr_assemble(const nksr_hier_t* h, const nksr_siteset_t* sets, int nsets, float reg, int col_bits,
                   void* workspace, const int32_t* rowptr, const int32_t* indeg, const int32_t* samelow,
                   const int32_t* mir_off, int col_format, int32_t* cols_out, float* vals_out, float* diag_out,

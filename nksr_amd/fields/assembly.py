@@ -1,4 +1,4 @@
-"""CSR assembly of a KernelField's normal equations (csrc/assemble.hip): the whole system of the assembled solve, or the
+"""CSR assembly of a KernelField's normal equations (csrc/gram.hip, assemble.hip, packed_rows.hip): the whole system of the assembled solve, or the
 diagonal block of the coarse levels for the preconditioner -- from site sets or from the rows a matrix-free operator holds."""
 import ctypes as C
 import time
@@ -55,6 +55,37 @@ def _sets_from_sites(fld, site_sets, hier, sets, keep):
     return len(site_sets)
 
 
+def _site_sets_and_structure(fld, hier, M, make_sets, too_large):
+    """What both assemblies start with: the site sets (``make_sets(sets, keep)`` fills them and returns their number) and the
+    structure pass -- own-upper counts and in-degrees of every row (nksr_assemble_count).  Returns (sets, nsets, keep, counts, ws,
+    n_up, n_mir, nnz, td): keep holds every buffer the sets point into, counts [4, M + 1] = rowcount, crosscount, samelow, indeg
+    (entry M of each is 0), ws is the workspace the fill shares with the pass, n_up / n_mir count the upper and the cross-level
+    (mirrored) entries, nnz those of the whole matrix; td is the timing tick.  ``too_large``: the caller's message, with (M, nnz),
+    for a system past 2^31 entries."""
+    if M == 0:
+        raise RuntimeError('empty hierarchy')
+    keep = []  # keep every buffer alive until the launches are enqueued
+    sets = (SiteSetT * 2)()
+    nsets = make_sets(sets, keep)
+    counts = torch.zeros((4, M + 1), dtype=torch.int32, device=fld.device)
+    ws = torch.empty(int(_lib.lib.nksr_assemble_workspace_bytes(C.byref(hier))), dtype=torch.uint8, device=fld.device)
+    td = _tick('_', time.perf_counter())
+    call('nksr_assemble_count', C.byref(hier), ptr(ws), ptr(counts[0]), ptr(counts[1]), ptr(counts[2]), ptr(counts[3]), stream())
+    n_up, n_mir = [int(v) for v in counts[:2].sum(dim=1, dtype=torch.int64).tolist()]
+    td = _tick('asm:count', td)
+    nnz = 2 * n_up + M
+    if nnz >= 2 ** 31 - 4096:
+        raise RuntimeError(too_large % (M, nnz))
+    return sets, nsets, keep, counts, ws, n_up, n_mir, nnz, td
+
+
+def _split_scratch(fld, hier):
+    """(scratch or None, bytes): coarse cells hold thousands of site rows; with this scratch the levels that split and have few cells
+    sum every cell's Gram block with several wavefronts (csrc/gram.hip).  Without it one wavefront per cell does: the same bits."""
+    nbytes = int(_lib.lib.nksr_assemble_split_bytes(C.byref(hier)))
+    return (torch.empty(nbytes, dtype=torch.uint8, device=fld.device) if nbytes else None), nbytes
+
+
 def assemble(fld, pos_xyz, normal_xyz, normal_value, pos_weight, normal_weight, reg_weight=1.0,
              pos_sorted_keys=None, normal_sorted_keys=None, coarse_from=None, fused_op=None):
     """Materialise the CSR normal equations.  Returns (rowptr, cols, vals, diag, b).
@@ -64,27 +95,18 @@ def assemble(fld, pos_xyz, normal_xyz, normal_value, pos_weight, normal_weight, 
     dev = fld.device
     hier = fld._hier if coarse_from is None else fld._coarse_hier(int(coarse_from))
     M = fld.svh.num_unknowns if coarse_from is None else fld.svh.num_unknowns - fld.svh.offsets[int(coarse_from)]
-    if M == 0:
-        raise RuntimeError('empty hierarchy')
-    keep = []  # keep every buffer alive until the launches are enqueued
-    sets = (SiteSetT * 2)()
     if fused_op is not None:
-        nsets = _sets_from_operator(fld, fused_op, coarse_from, sets, keep)
+        def make_sets(sets, keep):
+            return _sets_from_operator(fld, fused_op, coarse_from, sets, keep)
     else:
-        nsets = _sets_from_sites(fld, fld._site_sets((pos_xyz, None, pos_weight, pos_sorted_keys),
-                                                     (normal_xyz, normal_value, normal_weight, normal_sorted_keys)), hier, sets, keep)
+        def make_sets(sets, keep):
+            return _sets_from_sites(fld, fld._site_sets((pos_xyz, None, pos_weight, pos_sorted_keys),
+                                                        (normal_xyz, normal_value, normal_weight, normal_sorted_keys)), hier, sets, keep)
     # structure pass: own-upper counts + in-degrees -> exclusive scans -> final CSR row pointers
-    counts = torch.zeros((4, M + 1), dtype=torch.int32, device=dev)
+    sets, nsets, keep, counts, ws, n_up, n_mir, nnz, td = _site_sets_and_structure(
+        fld, hier, M, make_sets, 'assembled system too large for one chunk (M=%d, nnz=%d >= 2^31): use the matrix-free solve '
+        '(fused_mode=True) or pass chunk_size= to reconstruct() (examples/recons_by_chunk.py)')
     rowcount, crosscount, samelow, indeg = counts[0], counts[1], counts[2], counts[3]
-    ws = torch.empty(int(_lib.lib.nksr_assemble_workspace_bytes(C.byref(hier))), dtype=torch.uint8, device=dev)
-    td = _tick('_', time.perf_counter())
-    call('nksr_assemble_count', C.byref(hier), ptr(ws), ptr(rowcount), ptr(crosscount), ptr(samelow), ptr(indeg), stream())
-    n_up, n_mir = [int(v) for v in counts[:2].sum(dim=1, dtype=torch.int64).tolist()]
-    td = _tick('asm:count', td)
-    nnz = 2 * n_up + M
-    if nnz >= 2 ** 31 - 4096:
-        raise RuntimeError('assembled system too large for one chunk (M=%d, nnz=%d >= 2^31): use the matrix-free solve '
-                           '(fused_mode=True) or pass chunk_size= to reconstruct() (examples/recons_by_chunk.py)' % (M, nnz))
     rowlen = indeg + samelow + rowcount + 1     # [cross-level mirrors][same-level lower][own upper][diagonal]
     rowlen[M] = 0
     rowptr = ops.exclusive_sum_i32(rowlen)
@@ -109,9 +131,7 @@ def assemble(fld, pos_xyz, normal_xyz, normal_value, pos_weight, normal_weight, 
     b = torch.empty(M, dtype=torch.float32, device=dev)
     mir_k = torch.empty(n_mir, dtype=torch.int64, device=dev)
     mir_v = torch.empty(n_mir, dtype=torch.float32, device=dev)
-    # coarse cells hold thousands of site rows: their Gram blocks are accumulated by several wavefronts each (csrc/assemble.hip)
-    split_bytes = int(_lib.lib.nksr_assemble_split_bytes(C.byref(hier), sum(int(sets[i].n) * int(sets[i].ncomp) for i in range(nsets))))
-    split = torch.empty(split_bytes, dtype=torch.uint8, device=dev) if split_bytes else None
+    split, split_bytes = _split_scratch(fld, hier)
     call('nksr_assemble', C.byref(hier), sets, nsets, float(reg_weight), col_bits, ptr(ws), ptr(rowptr), ptr(indeg),
          ptr(samelow), ptr(mir_off), fmt, ptr(cols), ptr(vals), ptr(diag), ptr(mir_k), ptr(mir_v), ptr(b), ptr(split), split_bytes, stream())
     td = _tick('asm:blocks+fill', td)
@@ -135,7 +155,7 @@ def assemble(fld, pos_xyz, normal_xyz, normal_value, pos_weight, normal_weight, 
 
 def assemble_packed(fld, reg_weight, coarse_from, fused_op, old_of_new, new_of_old, local_col, drop):
     """The packed (format 1) diagonal block of the levels >= ``coarse_from`` straight from the row fill (csrc/assemble.hip,
-    nksr_assemble_packed): the drop test runs where an entry is formed, so neither the fp32 CSR of the block nor the mirrors of the
+    nksr_assemble_packed; its rows: csrc/packed_rows.hip): the drop test runs where an entry is formed, so neither the fp32 CSR of the block nor the mirrors of the
     dropped entries exist.  ``old_of_new`` / ``new_of_old``: the segment-major renumbering (int32), ``local_col`` = new_of_old -
     seg_base[segment].  Returns (packed, packed_rowptr, dis, kept, nnz, diag): the arrays nksr_coarse_pack makes of the CSR, word for
     word, the structural entry count of the block, and its diagonal in the old order."""
@@ -143,21 +163,9 @@ def assemble_packed(fld, reg_weight, coarse_from, fused_op, old_of_new, new_of_o
     c0 = int(coarse_from)
     hier = fld._coarse_hier(c0)
     M = fld.svh.num_unknowns - fld.svh.offsets[c0]
-    if M == 0:
-        raise RuntimeError('empty hierarchy')
-    keep = []
-    sets = (SiteSetT * 2)()
-    nsets = _sets_from_operator(fld, fused_op, c0, sets, keep)
-    counts = torch.zeros((4, M + 1), dtype=torch.int32, device=dev)
-    rowcount, crosscount, samelow, indeg = counts[0], counts[1], counts[2], counts[3]
-    ws = torch.empty(int(_lib.lib.nksr_assemble_workspace_bytes(C.byref(hier))), dtype=torch.uint8, device=dev)
-    td = _tick('_', time.perf_counter())
-    call('nksr_assemble_count', C.byref(hier), ptr(ws), ptr(rowcount), ptr(crosscount), ptr(samelow), ptr(indeg), stream())
-    n_up, n_mir = [int(v) for v in counts[:2].sum(dim=1, dtype=torch.int64).tolist()]
-    td = _tick('asm:count', td)
-    nnz = 2 * n_up + M
-    if nnz >= 2 ** 31 - 4096:
-        raise RuntimeError('coarse block too large (M=%d, nnz=%d >= 2^31)' % (M, nnz))
+    sets, nsets, keep, counts, ws, n_up, n_mir, nnz, td = _site_sets_and_structure(
+        fld, hier, M, lambda sets, keep: _sets_from_operator(fld, fused_op, c0, sets, keep), 'coarse block too large (M=%d, nnz=%d >= 2^31)')
+    rowcount, crosscount, samelow = counts[0], counts[1], counts[2]
     own_off = ops.exclusive_sum_i32(samelow + rowcount)        # (entry M of both is 0)
     mir_off = ops.exclusive_sum_i32(crosscount)
     own = torch.empty(max(2 * n_up - n_mir, 1), dtype=torch.int32, device=dev)     # same-level lower (= same-level upper) + own upper
@@ -165,8 +173,7 @@ def assemble_packed(fld, reg_weight, coarse_from, fused_op, old_of_new, new_of_o
     kept = torch.empty((3, M + 1), dtype=torch.int32, device=dev)
     kept[:, M] = 0
     diag = torch.empty(M, dtype=torch.float32, device=dev)
-    split_bytes = int(_lib.lib.nksr_assemble_split_bytes(C.byref(hier), sum(int(sets[i].n) * int(sets[i].ncomp) for i in range(nsets))))
-    split = torch.empty(split_bytes, dtype=torch.uint8, device=dev) if split_bytes else None
+    split, split_bytes = _split_scratch(fld, hier)
     call('nksr_assemble_packed', C.byref(hier), sets, nsets, float(reg_weight), ptr(ws), ptr(samelow), ptr(mir_off), ptr(own_off),
          ptr(new_of_old), ptr(local_col), float(drop), ptr(diag), ptr(own), ptr(mir), ptr(kept), ptr(split), split_bytes, stream())
     td = _tick('asm:blocks+fill', td)

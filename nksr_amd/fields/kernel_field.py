@@ -9,7 +9,7 @@ reg_weight=)`` :105-112; fused ``solve`` selected by ``fused_mode`` examples/rec
 Math: unknowns alpha (one per voxel per level, levels
 concatenated fine -> coarse), f(x) = sum_d sum_{j in N27(x)} alpha_j <phi_d(x), psi_j> B(.),
 normal equations (w_p G^T G + w_n Q^T Q + reg I) alpha = w_n Q^T n solved by Jacobi-PCG.
-All numeric work runs in HIP kernels (csrc/kfield.hip, assemble.hip, spmv.hip, cheb.hip, pcg.hip).
+All numeric work runs in HIP kernels (csrc/kfield.hip, gram.hip, assemble.hip, packed_rows.hip, spmv.hip, cheb.hip, pcg.hip).
 
 This module holds the field: its API, the solve policies and the evaluation.  The set-up of a solve lives beside it:
 assembly.py (CSR assembly), operator_setup.py + row_layout.py (matrix-free operator), coarse_precond.py (coarse-level

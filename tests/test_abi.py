@@ -294,6 +294,6 @@ def test_c_abi_argument_errors_without_a_gpu():
     empty = _lib.LevelT()                            # a level without voxels only fills `out`: that one is still checked
     assert lib.nksr_udf_decode(C.byref(empty), 0, Z, Z, 3, f1, f1, 0, Z, Z) != 0 and 'NULL' in err()
     assert lib.nksr_udf_decode(C.byref(empty), 0, Z, Z, 3, f1, f1, 1, A, Z) == 0       # only_unset: nothing to do, nothing launched
-    assert lib.nksr_assemble_split_bytes(C.byref(h), C.c_int64(10 ** 6)) == 0           # no voxels: nothing to split
+    assert lib.nksr_assemble_split_bytes(C.byref(h)) == 0           # no voxels: nothing to split
     with __import__('pytest').raises(RuntimeError):
         _lib.call('nksr_pack_cols21', null, 100, null, null)

@@ -1,4 +1,4 @@
-"""The packed coarse-level block straight from the row fill (csrc/assemble.hip: k_row_diag, k_row_fill<.., true>, k_pk_*; fields/assembly.py:
+"""The packed coarse-level block straight from the row fill (csrc/assemble.hip: k_row_diag, k_row_fill<.., true>; csrc/packed_rows.hip: k_pk_*; fields/assembly.py:
 assemble_packed) against the path it replaces on the same field: fld.assemble(coarse_from=..., fused_op=op) -- the fp32 CSR -- followed
 by _pack_block (nksr_coarse_pack_count / nksr_coarse_pack), which coarse_precond still takes with {'direct': False}.
 
@@ -197,7 +197,7 @@ def test_early_diagonal_is_the_fills_bit_for_bit(name, row_format):
 @pytest.mark.parametrize('name', ['depth5', 'depth5x2'])
 def test_level_aligned_gram_loads_give_the_site_set_blocks_bit_for_bit(name, row_format, monkeypatch):
     """The Gram kernels read the operator's row list with tile n = level d + n (asm_lm_pointers); handed over as a site set WITH a row
-    index (the identity) the same rows go through asm_accumulate_rows, whose loads and column map are the concatenated-levels ones.
+    index (the identity) the same rows go through gram_rows (csrc/gram.hip), whose loads and column map are the concatenated-levels ones.
     Both get the rows' targets as right-hand side, so the spare lane that carries it is compared too (b is not all zero).  Depth 5:
     three, two and one column tiles."""
     from nksr_amd._lib import ptr
@@ -221,3 +221,69 @@ def test_level_aligned_gram_loads_give_the_site_set_blocks_bit_for_bit(name, row
     for k, a, b in zip(('rowptr', 'cols', 'vals', 'diag', 'b'), out[False], out[True]):
         assert torch.equal(_bits(a), _bits(b)), '%s differs in %d of %d words' % (k, int((_bits(a) != _bits(b)).sum()), a.numel())
     assert float(out[False][4].abs().max()) > 0
+
+
+def _level_parts(d):
+    """asm_level_parts of csrc/gram.hip: the parts a level's cells are cut into at most"""
+    return min(4 ** (d - 2), 64) if d >= 3 else 1
+
+
+SPLIT_CASES = [('depth5', 'list'), ('depth5x2', 'list'), ('depth5x2', 'indexed'), ('depth4', 'sites')]
+
+
+@pytest.mark.parametrize('name,source', SPLIT_CASES, ids=['%s-%s' % c for c in SPLIT_CASES])
+def test_split_schedules_give_the_same_blocks_bit_for_bit(name, source, monkeypatch):
+    """csrc/gram.hip cuts the rows of a cell of a level >= 3 into parts and promises the same block from both schedules of the parts:
+    one wavefront per (cell, part) and a reduction through the split scratch (k_cell_blocks_part / _reduce: what every fixture of this
+    size runs) and one wavefront per cell (k_cell_blocks_seq: what a level of more than 65536 (cell, part) pairs runs, the batched scene
+    among them).  The same assembly with the scratch and without it, every returned tensor word for word.
+    'list': the coarse block from the operator's row list (asm_accumulate_lm inside the split kernels); 'indexed': the same rows as a
+    site set with the identity row index and their targets (gram_rows inside them, and a right-hand side); 'sites': the whole
+    site-major system of the cloud, whose coarsest level splits."""
+    from nksr_amd._lib import ptr
+    from nksr_amd.fields import assembly
+    fld, op, seg = _operator(name, 'dense')
+    svh, _, _, _, xyz, nrm, nval = _field(name)
+    off = fld.svh.offsets
+    if source == 'sites':
+        args = (_t(xyz), _t(nrm), _t(nval), 1e4 / len(xyz), 1e2 / len(nrm), 1.0)
+        kwargs = {}
+        rows = [0] * fld.svh.depth
+        for ss in fld._site_sets((args[0], None, args[3], None), (args[1], args[2], args[4], None)):
+            st, en = fld._site_ranges(ss.keys)
+            rows = [r + (e - s).long() * ss.rows for r, s, e in zip(rows, st, en)]
+    else:
+        args, kwargs = (None, None, None, 1.0, 1.0, 1.0), dict(coarse_from=C0, fused_op=op)
+        per_cell = (op['span'][1] - op['span'][0] + 1).long() * (op['span'][0] >= 0)
+        rows = [per_cell[off[d]:off[d] + fld.svh.level(d).num_voxels] for d in range(fld.svh.depth)]
+        if source == 'indexed':
+            plain = assembly._sets_from_operator
+            ident = torch.arange(op['rows_total'], dtype=torch.int32, device=_dev())
+
+            def sets_from_operator(fld_, fused_op, coarse_from, sets, keep):
+                nsets = plain(fld_, fused_op, coarse_from, sets, keep)
+                sets[0].target, sets[0].row_index = ptr(fused_op['targets_all']), ptr(ident)
+                return nsets
+            monkeypatch.setattr(assembly, '_sets_from_operator', sets_from_operator)
+    # the fixture holds its case: a level that splits has a cell of at least two parts, and few enough (cell, part) pairs for the
+    # parallel schedule, whose scratch the first run is given
+    split = [d for d in range(3, fld.svh.depth) if int(rows[d].max()) >= 256 and rows[d].numel() * _level_parts(d) <= 65536]
+    assert split, [(d, int(rows[d].max()), rows[d].numel()) for d in range(fld.svh.depth)]
+    given = []
+    real = assembly._split_scratch
+
+    def recorded(*a):
+        given.append(real(*a))
+        return given[-1]
+    monkeypatch.setattr(assembly, '_split_scratch', recorded)
+    par = fld.assemble(*args, **kwargs)
+    assert len(given) == 1 and given[0][0] is not None and given[0][1] > 0
+    monkeypatch.setattr(assembly, '_split_scratch', lambda *a: (None, 0))
+    seq = fld.assemble(*args, **kwargs)
+    pu.report('split_schedules:%s:%s' % (name, source), levels=str(split), largest_cell=str([int(rows[d].max()) for d in split]),
+              cells=str([rows[d].numel() for d in split]), scratch_bytes=given[0][1])
+    for k, a, b in zip(('rowptr', 'cols', 'vals', 'diag', 'b'), par, seq):
+        assert a.dtype == b.dtype and a.shape == b.shape, k
+        assert torch.equal(_bits(a), _bits(b)), '%s differs in %d of %d words' % (k, int((_bits(a) != _bits(b)).sum()), a.numel())
+    if source != 'list':
+        assert float(par[4].abs().max()) > 0
