@@ -417,7 +417,8 @@ int nksr_coarse_lambda_max(const int32_t* rowptr, const int32_t* cols, const flo
 int nksr_coarse_precond_apply(const nksr_coarse_precond_t* pc, int32_t nseg, const float* r, float* z, void* stream);
 
 /* ---- matrix-free ("fused") operator and solve: reconstruct(..., fused_mode=True), examples/recons_waymo.py:33,
- *      recons_waymo_cpu.py:58, gis_app.py:40; KernelField.solve (csrc/fused.hip).  The system matrix is never built:
+ *      recons_waymo_cpu.py:58, gis_app.py:40; KernelField.solve (csrc/fused_tables.hip: the tables, csrc/fused_sweep.hip: the pass over the rows, csrc/fused.hip:
+ *      the second product, these entry points and the solve).  The system matrix is never built:
  *      y = (sum_s R_s^T R_s + reg I) x is applied from the dense-slot kernel rows, cell by cell. ------------------ */
 typedef struct {
     int32_t depth, M, n_multi, n_big;

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libnksr_hip.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'nksr_hip.h')     # the C ABI: a source of the library, and what _lib.py binds from
-SOURCES = ['prims.hip', 'hierarchy.hip', 'kfield.hip', 'rows.hip', 'evalf.hip', 'gram.hip', 'assemble.hip', 'packed_rows.hip', 'spmv.hip', 'cheb.hip', 'pcg.hip', 'fused.hip', 'meshing.hip', 'nn.hip', 'knn.hip', 'chunks.hip', 'metrics.hip', 'meshquery.hip', 'meshtopo.hip', 'meshgeom.hip', 'meshsimp.hip', 'cloud.hip', 'orient.hip']
+SOURCES = ['prims.hip', 'hierarchy.hip', 'kfield.hip', 'rows.hip', 'evalf.hip', 'gram.hip', 'assemble.hip', 'packed_rows.hip', 'spmv.hip', 'cheb.hip', 'pcg.hip', 'fused_tables.hip', 'fused_sweep.hip', 'fused.hip', 'meshing.hip', 'nn.hip', 'knn.hip', 'chunks.hip', 'metrics.hip', 'meshquery.hip', 'meshtopo.hip', 'meshgeom.hip', 'meshsimp.hip', 'cloud.hip', 'orient.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result'] + os.environ.get('NKSR_EXTRA_HIPCC_FLAGS', '').split()
 
@@ -39,8 +39,11 @@ def source_hash():
     return h.hexdigest()
 
 
-KERNEL_SOURCES = {'fused': ['fused.hip', 'pcg_core.h', 'common.h'],      # k_fz_sweep / k_fz_gather / k_fz_cellsum
-                  'spmv': ['spmv.hip', 'spmv.h', 'common.h']}            # k_spmv / k_spmv_fixup
+# The files each family of roofline kernels is compiled from: the .hip files that define them and every header under csrc/ those
+# include (tests/test_bench_contract_cpu.py checks the lists against the sources).  The operator's tables (fused_tables.hip) run
+# once per solve and are not among them.
+KERNEL_SOURCES = {'fused': ['fused_sweep.hip', 'fused.hip', 'fused_dev.h', 'pcg_core.h', 'common.h'],      # k_fz_cells / k_fz_gather / k_fz_cellsum
+                  'spmv': ['spmv.hip', 'spmv.h', 'common.h']}                                              # k_spmv / k_spmv_fixup
 
 
 def kernel_hash(kind):

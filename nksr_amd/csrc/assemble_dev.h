@@ -4,6 +4,7 @@
 // symbols stay out of its dynamic table.  (Not in common.h: build.kernel_hash covers that file for the roofline kernels.)
 #pragma once
 #include "common.h"
+#include "hier_dev.h"
 #include <type_traits>
 
 #define ASM_WAVES 1
@@ -45,12 +46,6 @@ static inline void asm_with_width(int v, F&& f) {
         if (v < MAX) return asm_with_width<MAX - 1>(v, f);
     }
     f(std::integral_constant<int, MAX>{});
-}
-
-__device__ __forceinline__ int row_level(const nksr_hier_t& h, int row) {
-    int d = 0;
-    while (d + 1 < h.depth && row >= h.lv[d + 1].offset) ++d;
-    return d;
 }
 
 // physical CSR layout (see csrc/spmv.hip): tiles of 64 EPL entries, logical entry m of a tile at

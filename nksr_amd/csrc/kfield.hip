@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(128) k_kernel_rows(nksr_hier_t hier, const flo
     }
 }
 
-// ---- rank-K FACTORS of the kernel rows (kernel_dim 4; the matrix-free solve, csrc/fused.hip) --------------------------------------
+// ---- rank-K FACTORS of the kernel rows (kernel_dim 4; the matrix-free solve rebuilds the rows from them: fz_rebuild_rows, csrc/fused_sweep.hip) ----
 // A dense-slot row is a rank-K object:  row[s] = B_s(u) <phi, psi_s>  (position rows),  d/dx_a: <phi, psi_s> dB_s/dx_a + <J_a, psi_s> B_s
 // with phi = phi_d(x) (K floats), J_a = d phi / d x_a, u = the local coordinate of x in its level-d cell -- and u follows from the
 // ONE fp32 product p = x * inv_w0 at every level (u_d = frac(p 2^-d)).  Instead of 108 bytes per row and level this writes

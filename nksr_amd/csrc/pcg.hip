@@ -3,7 +3,7 @@
 //             spmv.h and common.h and nothing of the two below
 //   cheb.hip  the coarse-level block preconditioner in both of its formats: Chebyshev steps, eigenvalue bounds, the CSR -> packed
 //             converter (drop rule and entry word: coarse_pack_dev.h, shared with assemble.hip)
-//   pcg.hip   this file: the segmented conjugate-gradient loop (nksr_pcg_run, which fused.hip drives with its own operator through
+//   pcg.hip   this file: the segmented conjugate-gradient loop (nksr_pcg_run, which fused.hip -- the matrix-free operator: fused_tables.hip, fused_sweep.hip, fused.hip -- drives with its own operator through
 //             pcg_core.h), its workspace, the live profiling of the operator launches, and the CSR solve nksr_pcg_solve
 // pcg_dev.h holds what the loop and the preconditioner share: SegScalars and the fixed-order reductions.
 // Per iteration: (1) y = A p, (2) partial dot p.y (own small kernel, see k_spcg_dot), (3) x,r,z update

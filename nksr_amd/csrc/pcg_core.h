@@ -1,5 +1,5 @@
 // Jacobi-PCG driver shared by the assembled-CSR solve (csrc/pcg.hip) and the matrix-free fused solve
-// (csrc/fused.hip): the iteration is the same, only y = A p differs.
+// (csrc/fused.hip; its sweep over the kernel rows is csrc/fused_sweep.hip): the iteration is the same, only y = A p differs.
 #pragma once
 #include "common.h"
 

@@ -1,4 +1,4 @@
-"""Set-up of the matrix-free operator of a KernelField (csrc/fused.hip, nksr_fused_op_t), in four steps: the site sets
+"""Set-up of the matrix-free operator of a KernelField (csrc/fused_tables.hip, fused_sweep.hip, fused.hip; nksr_fused_op_t), in four steps: the site sets
 (KernelField._site_sets, shared with the assembly), the row layout, the row fill and the operator's tables."""
 import ctypes as C
 import os
@@ -156,7 +156,7 @@ def operator_tables(fld, R, item_seg, segments):
 
 def fused_operator(fld, pos_xyz, normal_xyz, normal_value, pos_weight, normal_weight, pos_sorted_keys=None, normal_sorted_keys=None,
                    pos_value=None, segments=None):
-    """Everything the matrix-free operator needs (csrc/fused.hip, nksr_fused_op_t): the level-major kernel rows of both
+    """Everything the matrix-free operator needs (csrc/fused_sweep.hip, fused.hip; nksr_fused_op_t): the level-major kernel rows of both
     site sets in one array (pre-multiplied by sqrt(weight)), their targets, the global neighbour table and the work
     items.  Returns a dict; ``keep`` holds the buffers the C struct points into."""
     if fld.svh.num_unknowns == 0:

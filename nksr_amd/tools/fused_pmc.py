@@ -71,7 +71,7 @@ def main():
     rec['hbm_bytes_per_application'] = tot
     import re
     m = re.search(r'M=(\d+) rows=(\d+) partial blocks=(\d+)', desc)
-    if m:      # same formula as csrc/fused.hip FusedOperator::bytes (depth 4 on the probe workload)
+    if m:      # same formula as csrc/fused.hip, FusedOperator::bytes (depth 4 on the probe workload)
         M, rows, blocks = int(m.group(1)), int(m.group(2)), int(m.group(3))
         rec['physical_bytes_per_application'] = 4 * 27 * 4 * rows + 4 * 4 * rows + 2 * 128 * blocks + (128 + 3 * 108 + 12) * M
         rec['algorithmic_note'] = 'algorithmic minimum (DESIGN.md section 3.5): 4 B per stored entry + 4 B per row and level + 116 B per unknown'

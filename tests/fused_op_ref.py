@@ -1,4 +1,4 @@
-"""Plain numpy / scipy restatement of the matrix-free operator (csrc/fused.hip, nksr_fused_op_t) and the crafted row layouts
+"""Plain numpy / scipy restatement of the matrix-free operator (csrc/fused_tables.hip, fused_sweep.hip, fused.hip; nksr_fused_op_t) and the crafted row layouts
 its sweep is tested on (tests/test_fused_op_ref_cpu.py, tests/test_gpu_fused_operator.py).
 
 The operator is completely defined by its arrays:

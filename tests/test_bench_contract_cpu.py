@@ -130,6 +130,37 @@ def test_stale_pmc_records_are_refused(tmp_path):
     assert build.kernel_hash('fused') != build.kernel_hash('spmv') and len(build.kernel_hash('spmv')) == 16
 
 
+def test_kernel_hash_covers_the_files_the_roofline_kernels_are_compiled_from():
+    """``build.KERNEL_SOURCES[kind]`` names every file under csrc/ that defines one of the family's kernels and every header under
+    csrc/ those files include, directly or through another header: an edit to any of them must invalidate the counter records.
+    The operator's tables (fused_tables.hip) run once per solve and are NOT among the 'fused' sources: an edit there leaves the
+    records of the operator valid."""
+    import re
+    from nksr_amd import build
+
+    def closure(files):
+        seen, todo = set(), list(files)
+        while todo:
+            f = todo.pop()
+            if f in seen:
+                continue
+            seen.add(f)
+            text = open(os.path.join(build.CSRC, f)).read()
+            todo += [h for h in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M) if os.path.exists(os.path.join(build.CSRC, h)) and '/' not in h]
+        return seen
+
+    def defining(names):
+        pat = re.compile(r'__global__[^;{]*?\b(%s)\s*\(' % '|'.join(names), re.S)
+        return {f for f in os.listdir(build.CSRC) if f.endswith(('.hip', '.h')) and pat.search(open(os.path.join(build.CSRC, f)).read())}
+
+    for kind, names in (('fused', ('k_fz_cells', 'k_fz_cellsum', 'k_fz_gather')), ('spmv', ('k_spmv',))):
+        files = defining(names)
+        assert files, kind
+        missing = closure(files) - set(build.KERNEL_SOURCES[kind])
+        assert not missing, (kind, sorted(missing))
+    assert 'fused_tables.hip' not in build.KERNEL_SOURCES['fused']
+
+
 def test_committed_bench_line_and_its_pmc_records():
     """The round's committed bench line (profiles/r05_bench.json): configs[4] is the top-level workload at N = 1, the configs[2]
     single-field workload and north_star's CSR SpMV KPI travel as sub-records, every roofline fraction is a fraction, and wherever

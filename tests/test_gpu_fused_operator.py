@@ -1,4 +1,4 @@
-"""The matrix-free operator (csrc/fused.hip) by itself, one crafted row layout at a time (tests/fused_op_ref.py: what each layout
+"""The matrix-free operator (csrc/fused_tables.hip, fused_sweep.hip, fused.hip) by itself, one crafted row layout at a time (tests/fused_op_ref.py: what each layout
 is for; tests/test_fused_op_ref_cpu.py asserts that it has that property):
 
   * its tables word for word against tables_ref, a restatement of what span / item_begin / counts / nbr32 / nbrT MEAN;

@@ -1,4 +1,4 @@
-"""The stored-entry count of the set-up sweep (csrc/fused.hip, k_fz_cells<1, ...>) by itself.
+"""The stored-entry count of the set-up sweep (csrc/fused_sweep.hip, k_fz_cells<1, ...>) by itself.
 
 The sweep shares no word between its workgroups: every workgroup leaves ONE count, by a plain store, in the scratch behind
 nksr_fused_op_t.nnz_counter (op['nnz_scratch']: one word per workgroup, no initial value), and k_fz_count_sum adds the words into
