@@ -939,6 +939,74 @@ int nksr_simp_place(const void* v, int v_float64, int64_t nv, const void* faces,
 int nksr_simp_cluster_means(const void* attr, int attr_float64, int64_t nv, int64_t channels, const uint32_t* cluster_start,
                             const uint32_t* vertex_ids_sorted, int64_t n_clusters, double* mean_out, void* stream);
 
+/* ---- mesh cross-sections (nksr_amd/mesh_slice.py: MeshSlicer; csrc/meshslice.hip) -------------------------
+ * One family of parallel planes { x : n . x = offsets[j] } (n a unit vector as three HOST doubles, offsets [P] fp64 on the device,
+ * finite and strictly ascending) cut into points on the unique edges of the topology section's edge table, one segment per (face,
+ * crossed plane) and polylines; the definition is DESIGN.md section 3.15, restated in numpy by tests/mesh_slice_ref.py.  Faces,
+ * validity and the limits as in the topology section, positions as in the geometry section; N points, S segments < 2^31.  No atomics:
+ * ids are exclusive scans plus offsets, every write has one writer, every floating-point sum is nksr_inclusive_sum_by_key_f64.
+ * Sequence: nksr_slice_heights, nksr_slice_counts, nksr_exclusive_sum_i64 of both count arrays (read N and S), nksr_slice_points,
+ * nksr_slice_segments, nksr_chain_rank over pred, nksr_exclusive_sum_i32 of rep_flags (read L), nksr_slice_rep_list, a stable
+ * nksr_sort_pairs_u64_u32 of (plane_key, position) over bit_length(P) bits: polyline l = entry l, nksr_slice_polyline_sizes,
+ * nksr_exclusive_sum_i32 of both size arrays, nksr_slice_polylines, nksr_inclusive_sum_by_key_f64 of both term arrays. */
+/* height_out [nv] fp64 = fma(n_z, z, fma(n_y, y, n_x x)), positions widened exactly; a height that is not a number is stored as -inf
+ * (such a vertex lies below every plane).  Vertex v is ABOVE plane j iff height[v] >= offsets[j]. */
+int nksr_slice_heights(const void* v, int v_float64, int64_t nv, const double* normal, double* height_out, void* stream);
+/* lo = the number of offsets <= the smallest height of a valid face's corners (an edge's end points), count = the number in
+ * (smallest, largest]: the item crosses the planes [lo, lo + count).  An invalid face: 0, 0.  face_lo_out [nf], face_count_out [nf + 1]
+ * (a closing 0, the input of the scan), edge_lo_out [n_edges], edge_count_out [n_edges + 1]; edges [n_edges, 2] = edge_v of the edge
+ * table.  The offsets are staged in LDS up to 2048 planes. */
+int nksr_slice_counts(const double* height, int64_t nv, const void* faces, int faces_int64, int64_t nf, const uint8_t* face_valid,
+                      const int32_t* edges, int64_t n_edges, const double* offsets, int64_t n_planes, int32_t* face_lo_out,
+                      int64_t* face_count_out, int32_t* edge_lo_out, int64_t* edge_count_out, void* stream);
+/* point point_start[e] + (j - edge_lo[e]) for every plane j the edge e = (a, b), a < b, crosses (point_start [n_edges + 1] = the scan
+ * of edge_count): points_out [N, 3] fp64 = a + t (b - a), t = (offsets[j] - h_a) / (h_b - h_a), every operation rounded on its own;
+ * point_edge_out / point_plane_out [N].  by_point = 0: one lane per edge, looping over its planes; != 0: one lane per point, which finds
+ * its edge by a binary search of point_start -- the same outputs. */
+int nksr_slice_points(const void* v, int v_float64, int64_t nv, const double* height, const int32_t* edges, int64_t n_edges,
+                      const double* offsets, int64_t n_planes, const int32_t* edge_lo, const int64_t* point_start, int64_t n_points,
+                      int by_point, double* points_out, int32_t* point_edge_out, int32_t* point_plane_out, void* stream);
+/* segment seg_start[f] + (j - face_lo[f]) for every plane j face f crosses (seg_start [nf + 1] = the scan of face_count):
+ * segments_out [S, 2] = (tail, head) = the points on the face's half-edge that goes above -> below and on the one that goes
+ * below -> above (half-edge k runs corner k -> corner k + 1; halfedge_edge [3 nf] = its unique edge); segment_face_out,
+ * segment_plane_out [S]; succ_out [S] = the segment of the same plane in face_adj[f, k] across the half-edge k that carries the head
+ * when that edge's class is NKSR_TOPO_INTERIOR, else -1; pred_out [S] likewise across the half-edge that carries the tail (succ is
+ * injective and pred its inverse). */
+int nksr_slice_segments(const double* height, int64_t nv, const void* faces, int faces_int64, int64_t nf, const double* offsets,
+                        int64_t n_planes, const int32_t* halfedge_edge, const uint8_t* edge_class, const int32_t* face_adj,
+                        const int32_t* face_lo, const int64_t* seg_start, const int32_t* edge_lo, const int64_t* point_start,
+                        int64_t n_segments, int32_t* segments_out, int32_t* segment_face_out, int32_t* segment_plane_out, int32_t* succ_out,
+                        int32_t* pred_out, void* stream);
+/* List ranking of n < 2^31 elements linked by pred [n] (the element one step nearer the start of its list; < 0, >= n or the element
+ * itself: none), where no two elements share a predecessor -- the inverse of any injective successor array.  The lists are open
+ * chains and cycles.  rep_out [n] = the representative: a chain's element without predecessor, a cycle's smallest element;
+ * rank_out [n] = the number of steps from the representative; cyclic_out [n] = 1 on a cycle; rep_flags_out [n + 1] = (rep == the
+ * element), then a 0 -- the input of nksr_exclusive_sum_i32, whose last entry is the number of lists.  Pointer doubling over two
+ * ping-pong buffers of 16 bytes per element (work: 32 n bytes, 16-byte aligned): nksr_chain_rank_rounds(n) = ceil(log2 n) + 1 rounds
+ * queued back to back, nothing is read on the host; chains and cycles are ranked in the same sweep (a window minimum with its distance
+ * finds and cuts a cycle at its smallest element).  The outputs are a function of pred alone. */
+int64_t nksr_chain_rank_rounds(int64_t n);
+int nksr_chain_rank(const int32_t* pred, int64_t n, void* work, int32_t* rep_out, int32_t* rank_out, uint8_t* cyclic_out,
+                    int32_t* rep_flags_out, void* stream);
+/* the representatives in ascending segment id: list_out[rep_dense[s]] = s and plane_key_out[rep_dense[s]] = segment_plane[s] where
+ * rep_flags[s] (rep_dense = the exclusive scan of rep_flags); [L] each */
+int nksr_slice_rep_list(const int32_t* rep_flags, const int32_t* rep_dense, int64_t n_segments, const int32_t* segment_plane,
+                        int64_t n_polylines, int32_t* list_out, uint64_t* plane_key_out, void* stream);
+/* segment_polyline_out [S] = polyline_of_dense[rep_dense[rep[s]]]; the last segment of a polyline (no successor, or its successor is
+ * the representative) writes n_segments_out[l] = m = rank + 1, n_points_out[l] = m on a cycle and m + 1 on an open chain, and
+ * closed_out[l]; both size arrays are [L + 1] with a closing 0 */
+int nksr_slice_polyline_sizes(const int32_t* rep, const int32_t* rank, const uint8_t* cyclic, const int32_t* succ, int64_t n_segments,
+                              const int32_t* rep_dense, const int32_t* polyline_of_dense, int64_t n_polylines, int32_t* segment_polyline_out,
+                              int32_t* n_segments_out, int32_t* n_points_out, uint8_t* closed_out, void* stream);
+/* polyline_points_out[point_offset[l] + rank] = the segment's tail, and behind the last segment of an open chain its head.  At
+ * segment_offset[l] + rank: term_key_out = l, length_term_out = sqrt(dx dx + dy dy + dz dz) of head - tail, area_term_out =
+ * 0.5 (n_x c_x + n_y c_y + n_z c_z) with c = (tail - p0) x (head - p0), p0 the tail of segment polyline_rep[l], on a cycle and 0 on an
+ * open chain; every operation rounded on its own, sums left to right.  (The offsets are the scans of the two size arrays.) */
+int nksr_slice_polylines(const int32_t* segments, const int32_t* rank, const uint8_t* cyclic, const int32_t* succ, int64_t n_segments,
+                         const int32_t* segment_polyline, const int32_t* polyline_rep, const int32_t* segment_offset,
+                         const int32_t* point_offset, int64_t n_polylines, const double* points, int64_t n_points, const double* normal,
+                         int32_t* polyline_points_out, uint64_t* term_key_out, double* length_term_out, double* area_term_out, void* stream);
+
 /* ---- normal orientation without sensors (csrc/orient.hip; nksr_amd/orient.py orient_graph) -------------
  * Hoppe et al. 1992: the minimum spanning forest of the k-nearest-neighbour graph under the weight 1 - |n_i . n_j|, sign flips
  * propagated along it.  DEFINITION (restated in tests/orient_ref.py; every output is a function of the input alone):

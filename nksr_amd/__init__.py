@@ -3,12 +3,13 @@
 Exports the surface of the reference's ``nksr`` package that its examples and training glue
 use: ``Reconstructor``, ``NKSRNetwork``, ``SparseFeatureHierarchy``,
 ``get_estimate_normal_preprocess_fn`` and the sub-modules ``fields``, ``svh``, ``configs``,
-``utils``; beyond it the mesh and point-cloud tools (``metrics``, ``MeshTopology``, ``MeshGeometry``, ``MeshSimplifier``, ``cloud`` and the
+``utils``; beyond it the mesh and point-cloud tools (``metrics``, ``MeshTopology``, ``MeshGeometry``, ``MeshSimplifier``, ``MeshSlicer``, ``cloud`` and the
 ``preprocess_fn`` makers on it).  ``import nksr`` resolves to this package through the top-level ``nksr`` shim.
 """
 from . import cloud, configs, fields, metrics, svh, utils
 from .mesh_geometry import MeshGeometry
 from .mesh_simplify import MeshSimplifier
+from .mesh_slice import MeshSlicer
 from .mesh_topology import MeshTopology
 from .nn.network import NKSRNetwork
 from .preprocess import (compose_preprocess_fns, get_estimate_normal_preprocess_fn, get_estimate_oriented_normal_preprocess_fn,
@@ -17,6 +18,6 @@ from .reconstructor import Reconstructor
 from .svh import SparseFeatureHierarchy
 
 __all__ = ['Reconstructor', 'NKSRNetwork', 'SparseFeatureHierarchy', 'get_estimate_normal_preprocess_fn', 'MeshTopology', 'MeshGeometry', 'MeshSimplifier',
-           'get_voxel_downsample_preprocess_fn', 'get_radius_outlier_preprocess_fn', 'get_statistical_outlier_preprocess_fn',
+           'MeshSlicer', 'get_voxel_downsample_preprocess_fn', 'get_radius_outlier_preprocess_fn', 'get_statistical_outlier_preprocess_fn',
            'get_estimate_oriented_normal_preprocess_fn', 'compose_preprocess_fns', 'fields', 'svh', 'configs', 'utils', 'metrics', 'cloud']
 __version__ = '0.1.0'

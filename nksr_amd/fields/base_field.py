@@ -55,6 +55,17 @@ class MeshingResult:
         r = MeshSimplifier(self.v, self.f, self.c).simplify(cell_size=cell_size, target_faces=target_faces, **kw)
         return MeshingResult(r.v2, r.f2, r.c2)
 
+    def slice(self, normal, offsets):
+        """``Sections`` of this mesh on the planes n . x = offsets[j] (``MeshSlicer.slice``, nksr_amd/mesh_slice.py): points on the
+        edges, one segment per face and plane, and the segments ordered into polylines with their lengths and signed areas."""
+        from ..mesh_slice import MeshSlicer
+        return MeshSlicer(self.v, self.f).slice(normal, offsets)
+
+    def contours(self, levels=None, interval=None, axis=2):
+        """``Sections`` at ``levels`` along ``axis``, or at the multiples of ``interval`` (``MeshSlicer.contours``)."""
+        from ..mesh_slice import MeshSlicer
+        return MeshSlicer(self.v, self.f).contours(levels=levels, interval=interval, axis=axis)
+
 
 class BaseField:
     def __init__(self, svh):

@@ -98,6 +98,27 @@ def write_obj_mesh(path, v, f, normals=None):
             out.write(''.join('f %d//%d %d//%d %d//%d\n' % (t[0], t[0], t[1], t[1], t[2], t[2]) for t in f))
 
 
+def write_obj_polylines(path, points, polyline_start, polyline_points, closed=None):
+    """Wavefront OBJ with one ``l`` element per polyline (``Sections`` of nksr_amd/mesh_slice.py): polyline k names the points
+    ``polyline_points[polyline_start[k]:polyline_start[k + 1]]``.  Positions are written with 17 significant digits, so fp64 points in a
+    projected coordinate system read back as they were.  ``closed`` [L] (optional): a flagged polyline repeats its first point at the
+    end."""
+    def host(x, dtype):
+        return np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, dtype)
+    p, start, ids = host(points, np.float64).reshape(-1, 3), host(polyline_start, np.int64).reshape(-1), host(polyline_points, np.int64).reshape(-1)
+    if len(start) == 0 or start[0] != 0 or np.any(start[1:] < start[:-1]) or start[-1] > len(ids):
+        raise ValueError('write_obj_polylines: polyline_start must ascend from 0 to at most %d' % len(ids))
+    if len(ids) and (ids.min() < 0 or ids.max() >= len(p)):
+        raise ValueError('write_obj_polylines: point index outside [0, %d)' % len(p))
+    loop = np.zeros(len(start) - 1, bool) if closed is None else host(closed, bool).reshape(-1)
+    with open(path, 'w') as out:
+        out.write(''.join('v %.17g %.17g %.17g\n' % (q[0], q[1], q[2]) for q in p))
+        for k in range(len(start) - 1):
+            row = ids[start[k]:start[k + 1]] + 1
+            if len(row):
+                out.write('l ' + ' '.join('%d' % i for i in (list(row) + [row[0]] if loop[k] else row)) + '\n')
+
+
 def warning_on_low_memory(threshold_mb):
     if torch.cuda.is_available():
         free, _ = torch.cuda.mem_get_info()
