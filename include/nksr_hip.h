@@ -1007,6 +1007,62 @@ int nksr_slice_polylines(const int32_t* segments, const int32_t* rank, const uin
                          const int32_t* point_offset, int64_t n_polylines, const double* points, int64_t n_points, const double* normal,
                          int32_t* polyline_points_out, uint64_t* term_key_out, double* length_term_out, double* area_term_out, void* stream);
 
+/* ---- mesh boundary loops and hole filling (nksr_amd/mesh_boundary.py: MeshBoundary; csrc/meshbound.hip) ----
+ * The boundary half-edges of the topology section's edge table ordered into loops, their measures, and the faces that close them; the
+ * definition is DESIGN.md section 3.16, restated in numpy by tests/mesh_boundary_ref.py.  Faces, validity and the limits as in the
+ * topology section, positions as in the geometry section; halfedge_edge [3 nf] = the unique edge of half-edge 3 f + k (corner k ->
+ * corner k + 1), -1 for an invalid face.  B boundary half-edges, L loops.  No floating-point atomic: ids are exclusive scans plus
+ * offsets, every write has one writer, every floating-point sum is nksr_inclusive_sum_by_key_f64; the boxes are integer min / max.
+ * Sequence: nksr_bnd_flags, nksr_exclusive_sum_i32 (boundary_of; its last entry is B), nksr_bnd_list, nksr_bnd_successor,
+ * nksr_chain_rank over pred, nksr_exclusive_sum_i32 of rep_flags (read L), nksr_bnd_loop_sizes, nksr_exclusive_sum_i32 of both size
+ * arrays, nksr_bnd_terms, nksr_inclusive_sum_by_key_f64 of the seven term rows, nksr_bnd_boxes; to fill: nksr_bnd_fill and
+ * nksr_bnd_fill_vertices. */
+/* flags_out [3 nf + 1] = 1 where the half-edge's unique edge has class NKSR_TOPO_BOUNDARY, then a 0 (the input of the scan) */
+int nksr_bnd_flags(const int32_t* halfedge_edge, const uint8_t* edge_class, int64_t nf, int64_t n_edges, int32_t* flags_out, void* stream);
+/* boundary id b = boundary_of[h] (the exclusive scan of flags) of every flagged half-edge h = 3 f + k: halfedge_out [B] = h,
+ * tail_out / head_out [B] = corners k and k + 1 of f, face_out [B] = f */
+int nksr_bnd_list(const void* faces, int faces_int64, int64_t nf, const int32_t* flags, const int32_t* boundary_of, int64_t n_boundary,
+                  int32_t* halfedge_out, int32_t* tail_out, int32_t* head_out, int32_t* face_out, void* stream);
+/* succ_out [B]: rotation about the head b of (a -> b) in f: the next half-edge (b -> c) of the face; BOUNDARY: its boundary id; INTERIOR:
+ * cross to face_adj, find the corner that holds (c -> b), continue with the half-edge after it; any other class: -1.  pred_out [B]: the
+ * mirrored walk about the tail.  succ is injective and pred its inverse; a walk takes at most valence steps and needs no guard. */
+int nksr_bnd_successor(const void* faces, int faces_int64, int64_t nf, const int32_t* halfedge_edge, const uint8_t* edge_class,
+                       const int32_t* face_adj, const int32_t* boundary_of, const int32_t* halfedge, int64_t n_boundary, int32_t* succ_out,
+                       int32_t* pred_out, void* stream);
+/* rep / rank / cyclic of nksr_chain_rank over pred, rep_dense the scan of its rep_flags: boundary_loop_out [B] = rep_dense[rep[b]] (loop
+ * ids ascend by representative), loop_rep_out [L]; the last half-edge of a loop writes loop_edges_out[l] = m = rank + 1,
+ * loop_points_out[l] = m on a cycle and m + 1 on an open chain, and closed_out[l]; both size arrays are [L + 1] with a closing 0 */
+int nksr_bnd_loop_sizes(const int32_t* rep, const int32_t* rank, const uint8_t* cyclic, const int32_t* succ, int64_t n_boundary,
+                        const int32_t* rep_dense, int64_t n_loops, int32_t* boundary_loop_out, int32_t* loop_rep_out, int32_t* loop_edges_out,
+                        int32_t* loop_points_out, uint8_t* closed_out, void* stream);
+/* loop_halfedges_out[edge_offset[l] + rank] = the half-edge, loop_vertices_out[point_offset[l] + rank] = its tail, and behind the last
+ * half-edge of an open chain its head.  terms_out [7, B] at column edge_offset[l] + rank, with p the tail, q the head, p0 the tail of
+ * loop_rep[l], a = p - p0, c = q - p0: row 0 w = sqrt(dx dx + dy dy + dz dz) of q - p; rows 1..3 0.5 (a x c) on a cycle, 0 on an open
+ * chain; rows 4..6 w (0.5 (a + c)); term_key_out = l there.  Every operation rounded on its own. */
+int nksr_bnd_terms(const void* v, int v_float64, int64_t nv, const int32_t* halfedge, const int32_t* tail, const int32_t* head,
+                   const int32_t* rank, const uint8_t* cyclic, const int32_t* succ, int64_t n_boundary, const int32_t* boundary_loop,
+                   const int32_t* loop_rep, const int32_t* edge_offset, const int32_t* point_offset, int64_t n_loops,
+                   int32_t* loop_halfedges_out, int32_t* loop_vertices_out, uint64_t* term_key_out, double* terms_out, void* stream);
+/* box_out [L, 6] fp64 = (min xyz, max xyz) over the tails and heads of every loop, by 64-bit order-preserving integer atomicMin /
+ * atomicMax in work [L, 6] (any contents) */
+int nksr_bnd_boxes(const void* v, int v_float64, int64_t nv, const int32_t* tail, const int32_t* head, const int32_t* boundary_loop,
+                   int64_t n_boundary, int64_t n_loops, uint64_t* work, double* box_out, void* stream);
+/* The new faces of the loops with keep[l] != 0, into faces_out [n_new_faces, 3] (int32, or int64 with faces_int64 != 0), appended loop
+ * by loop from face_offset[l], in rank order; face_loop_out [n_new_faces] = l.  method 0 ('centroid'): the half-edge (a -> b) of rank r
+ * gives face face_offset[l] + r = (b, a, nv + kept_rank[l]).  method 1 ('fan'): for 1 <= r <= m - 2 face face_offset[l] + r - 1 =
+ * (b, a, p0), p0 the tail of loop_rep[l].  Both wind against the boundary half-edges. */
+int nksr_bnd_fill(const int32_t* tail, const int32_t* head, const int32_t* rank, const int32_t* boundary_loop, int64_t n_boundary,
+                  const int32_t* loop_rep, const int32_t* loop_edges, const uint8_t* keep, const int32_t* kept_rank, const int32_t* face_offset,
+                  int64_t n_loops, int method, int64_t nv, int64_t n_new_faces, void* faces_out, int faces_int64, int32_t* face_loop_out,
+                  void* stream);
+/* v_out [n_kept, 3] (fp32, or fp64 with v_float64 != 0): row kept_rank[l] = loop_centroid[l] cast once; color_mean_out [n_kept,
+ * channels] fp64 = the mean of colors [nv, channels] (fp32, or fp64 with colors_float64 != 0) over the loop's vertices, summed in fp64
+ * in rank order (channels = 0: colors and color_mean_out NULL).  One lane per (loop, output column). */
+int nksr_bnd_fill_vertices(const double* loop_centroid, const int32_t* point_offset, const int32_t* loop_vertices, const int32_t* loop_edges,
+                           const uint8_t* keep, const int32_t* kept_rank, int64_t n_loops, int64_t n_kept, const void* colors,
+                           int colors_float64, int64_t channels, int64_t nv, void* v_out, int v_float64, double* color_mean_out,
+                           void* stream);
+
 /* ---- normal orientation without sensors (csrc/orient.hip; nksr_amd/orient.py orient_graph) -------------
  * Hoppe et al. 1992: the minimum spanning forest of the k-nearest-neighbour graph under the weight 1 - |n_i . n_j|, sign flips
  * propagated along it.  DEFINITION (restated in tests/orient_ref.py; every output is a function of the input alone):

@@ -66,6 +66,21 @@ class MeshingResult:
         from ..mesh_slice import MeshSlicer
         return MeshSlicer(self.v, self.f).contours(levels=levels, interval=interval, axis=axis)
 
+    def boundary_loops(self):
+        """``BoundaryLoops`` of this mesh (``MeshBoundary.loops``, nksr_amd/mesh_boundary.py): the boundary edges ordered into loops
+        with their edge counts, lengths, areas, centroids and boxes."""
+        from ..mesh_boundary import MeshBoundary
+        return MeshBoundary(self.v, self.f).loops()
+
+    def fill_holes(self, max_edges=None, max_length=None, max_area=None, method='centroid'):
+        """A new ``MeshingResult`` with the closed, simple boundary loops at or under the thresholds closed (``BoundaryLoops.select``,
+        ``MeshBoundary.fill``), ``c`` carried through.  Without a threshold every closed loop is filled, the rim of an open surface
+        included."""
+        from ..mesh_boundary import MeshBoundary
+        b = MeshBoundary(self.v, self.f)
+        v, f, c, _, _ = b.fill(b.loops().select(max_edges, max_length, max_area), method, self.c)
+        return MeshingResult(v, f, c)
+
 
 class BaseField:
     def __init__(self, svh):

@@ -38,7 +38,7 @@ import math
 import numpy as np
 import torch
 
-from . import ops
+from . import mesh_topology, ops
 from ._lib import call, lib, ptr, stream, with_tmp
 from .mesh_input import is64
 from .mesh_topology import MeshTopology
@@ -54,12 +54,9 @@ def _normal3(normal):
 
 # ---- stages (nksr_amd/tools/prof_mesh_slice.py times them one by one) ---------------------------------------------------------------
 def halfedge_edges(keys_sorted, ids_sorted, nv):
-    """[3F] int32: the unique edge of every half-edge 3 f + k (-1 for an invalid face): the run of its sorted key (``ops.sorted_runs``,
-    the edge table's own runs) scattered through the sort's permutation.  Syncs once (the number of runs)."""
-    _, _, _, run_of = ops.sorted_runs(keys_sorted, none_from=(nv << 32) | nv, run_of=True)
-    he = torch.empty_like(run_of)
-    he[ids_sorted.long()] = run_of                      # (a permutation of [0, 3F): every entry is written)
-    return he
+    """[3F] int32: the unique edge of every half-edge 3 f + k (-1 for an invalid face); ``mesh_topology.halfedge_edges``, which
+    ``MeshTopology.halfedge_edge`` computes once for the slicer and the boundary loops alike."""
+    return mesh_topology.halfedge_edges(keys_sorted, ids_sorted, nv)
 
 
 def heights(x, normal):
@@ -179,7 +176,7 @@ class MeshSlicer:
         self.v, self.f = t.v, t.f
         self.x = t.v if t.v.dtype in (torch.float32, torch.float64) else t.v32        # what the kernels read
         self.n_vertices, self.n_faces = t.n_vertices, t.n_faces
-        self.halfedge_edge = halfedge_edges(t._keys_sorted, t._ids_sorted, t.n_vertices)
+        self.halfedge_edge = t.halfedge_edge
 
     # ---- arguments ----
     @staticmethod

@@ -65,6 +65,15 @@ def edge_runs(f, nv, ks, ids_sorted, ref):
     return t
 
 
+def halfedge_edges(keys_sorted, ids_sorted, nv):
+    """[3F] int32: the unique edge of every half-edge 3 f + k (-1 for an invalid face): the run of its sorted key (``ops.sorted_runs``,
+    the edge table's own runs) scattered through the sort's permutation.  Syncs once (the number of runs)."""
+    _, _, _, run_of = ops.sorted_runs(keys_sorted, none_from=(nv << 32) | nv, run_of=True)
+    he = torch.empty_like(run_of)
+    he[ids_sorted.long()] = run_of                      # (a permutation of [0, 3F): every entry is written)
+    return he
+
+
 def union_find(n, valid, pairs):
     """(labels [n] int32, number of components) of the graph on n nodes: hook + flatten, dense ids in the order of the components'
     minimum node index (syncs once: the number of components)."""
@@ -167,6 +176,15 @@ class MeshTopology:
         self.edges, self.edge_counts = self._table.edges, self._table.edge_counts
         self.edge_classes, self.face_adjacency = self._table.edge_classes, self._table.face_adjacency
         self._components = {}
+        self._halfedge_edge = None
+
+    @property
+    def halfedge_edge(self):
+        """[3F] int32: the unique edge of half-edge 3 f + k, -1 for an invalid face (``halfedge_edges``; computed on first use and
+        kept: the slicer and the boundary loops share it)."""
+        if self._halfedge_edge is None:
+            self._halfedge_edge = halfedge_edges(self._keys_sorted, self._ids_sorted, self.n_vertices)
+        return self._halfedge_edge
 
     @property
     def euler_characteristic(self):
