@@ -603,6 +603,39 @@ int nksr_radius_count(const float* xyz_sorted, int64_t n_ref, const int32_t* sta
                       const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* query, int64_t nq, float radius,
                       int32_t cap, int exclude_self, const int32_t* self_index, int32_t* count_out, void* stream);
 
+/* ---- rigid registration: one ICP pass (csrc/register.hip; nksr_amd/register.py: cloud.icp) -----------------------------------
+ * nksr_icp_accumulate: one lane per source point s (fp32 [n_src, 3]).  p = R s + t in fp64, transform [12] (device) = the upper three
+ * rows of the 4 x 4 matrix, row-major: p_a = ((T[4a] s_x + T[4a+1] s_y) + T[4a+2] s_z) + T[4a+3], every product and sum rounded on its
+ * own (no fused multiply-add, here and in every term below: the terms are the ones plain fp64 arithmetic gives).  p32 = fl32(p)
+ * serves the search only: the nearest point q of the grid (arguments as nksr_radius_count takes them; cell >= radius) among the 27
+ * cells around p32 with knn_d2(p32 - q) <= fl32(radius)^2; on an exact tie the point with the smallest perm [n_ref] (int64: the grid's
+ * order -> the caller's).  A p32 that is not finite or has |p32| * inv_cell >= 2^20 - 8 on an axis has no correspondence.
+ * corr_out [n_src] (int64) = perm of that point, or -1.  partials_out [ceil(n_src / NKSR_ICP_BLOCK), NKSR_ICP_FIELDS] = per workgroup
+ * the fp64 sums over its points with a correspondence, reduced in a fixed order (wavefront butterfly, then the waves in order; no
+ * atomics), with d = p - q, p' = p - c, q' = q - c, c = centre [3] (device), |d|^2 = (d_x d_x + d_y d_y) + d_z d_z:
+ *   both methods   [NKSR_ICP_COUNT] the count, [NKSR_ICP_D2] sum |d|^2
+ *   method 0 (point)  [NKSR_ICP_PT_P + a] sum p'_a, [NKSR_ICP_PT_Q + a] sum q'_a, [NKSR_ICP_PT_PQ + 3 a + b] sum p'_a q'_b
+ *   method 1 (plane, normal_sorted [n_ref, 3] = the normals n in the grid's order): r = (n_x d_x + n_y d_y) + n_z d_z,
+ *     J = (p' x n, n) with (p' x n)_x = p'_y n_z - p'_z n_y (cyclic); [NKSR_ICP_PL_JJ + k] sum J_a J_b over a <= b, row after row
+ *     (k = 0 .. 20), [NKSR_ICP_PL_JR + a] sum J_a r, [NKSR_ICP_PL_RR] sum r^2
+ * and zeros in the fields a method does not use.  n_src == 0: nothing is touched.
+ * nksr_icp_reduce: sums_out [NKSR_ICP_FIELDS] = the column sums of partials [nrows, NKSR_ICP_FIELDS], one workgroup, fixed order. */
+#define NKSR_ICP_BLOCK 256
+#define NKSR_ICP_FIELDS 32
+#define NKSR_ICP_COUNT 0
+#define NKSR_ICP_D2 1
+#define NKSR_ICP_PT_P 2
+#define NKSR_ICP_PT_Q 5
+#define NKSR_ICP_PT_PQ 8
+#define NKSR_ICP_PL_JJ 2
+#define NKSR_ICP_PL_JR 23
+#define NKSR_ICP_PL_RR 29
+int nksr_icp_accumulate(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                        const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const int64_t* perm, const float* normal_sorted,
+                        const float* source, int64_t n_src, const double* transform, const double* centre, float radius, int method,
+                        int64_t* corr_out, double* partials_out, void* stream);
+int nksr_icp_reduce(const double* partials, int64_t nrows, double* sums_out, void* stream);
+
 /* ---- voxel reduction of a point cloud (csrc/cloud.hip; nksr_amd/cloud.py voxel_downsample) -----------------------------------
  * order [n] = point indices sorted by voxel key, start / end [n_vox] = the run of every voxel in it (nksr_run_table_u64 of the sorted
  * keys: start_out without its last entry, and without its first). mean_xyz_out [n_vox, 3] and mean_attr_out [n_vox, C] = the mean of xyz [n, 3] and of attr [n, C] (C = 0: attr and

@@ -3,7 +3,8 @@
 Exports the surface of the reference's ``nksr`` package that its examples and training glue
 use: ``Reconstructor``, ``NKSRNetwork``, ``SparseFeatureHierarchy``,
 ``get_estimate_normal_preprocess_fn`` and the sub-modules ``fields``, ``svh``, ``configs``,
-``utils``; beyond it the mesh and point-cloud tools (``metrics``, ``MeshTopology``, ``MeshGeometry``, ``MeshSimplifier``, ``MeshSlicer``, ``MeshBoundary``, ``cloud`` and the
+``utils``; beyond it the mesh and point-cloud tools (``metrics``, ``MeshTopology``, ``MeshGeometry``, ``MeshSimplifier``, ``MeshSlicer``, ``MeshBoundary``, ``cloud`` -- neighbour queries, voxel downsampling, outlier masks, normal
+orientation and rigid registration (``cloud.icp`` / ``icp_multiscale`` / ``evaluate_registration`` / ``apply_transform``) -- and the
 ``preprocess_fn`` makers on it).  ``import nksr`` resolves to this package through the top-level ``nksr`` shim.
 """
 from . import cloud, configs, fields, metrics, svh, utils

@@ -11,6 +11,8 @@ the neighbour search the package already runs for its normals, its SDF ground tr
   * ``radius_outlier_mask`` / ``statistical_outlier_mask``.
   * ``orient_graph`` / ``orient_normals`` / ``estimate_normals`` (nksr_amd/orient.py, csrc/orient.hip): oriented normals for a cloud
     that has positions only -- signs propagated along the minimum spanning forest of the kNN graph.
+  * ``icp`` / ``icp_multiscale`` / ``evaluate_registration`` / ``apply_transform`` / ``IcpResult`` (nksr_amd/register.py,
+    csrc/register.hip): rigid registration of one cloud onto another, point-to-point or point-to-plane, before scans are merged.
 ``nksr_amd.preprocess`` wraps them as ``preprocess_fn`` for ``Reconstructor.reconstruct``.  GPU tensors only.
 """
 import torch
@@ -19,6 +21,7 @@ from . import ops
 from ._lib import call, ptr, require_gpu, stream
 from .neighbours import MAX_K, _RINGS, PointGrid, PointPyramid, _grid_args, choose_cell_size, search_every_scale
 from .orient import OrientedNormals, estimate_normals, orient_graph, orient_normals  # noqa: F401  (part of this module's surface)
+from .register import IcpResult, apply_transform, evaluate_registration, icp, icp_multiscale  # noqa: F401  (part of this module's surface)
 from .svh import inv_w0_f32
 
 
@@ -64,6 +67,7 @@ class CloudIndex:
         self.pyramid = PointPyramid(PointGrid(self.xyz, cell))
         self.pg = self.pyramid.pg
         self._radius_grids = {}
+        self._centre = None
 
     # ---- helpers -------------------------------------------------------------------------------------------------------------
     def _queries(self, query, cell):
@@ -172,6 +176,20 @@ class CloudIndex:
         out = torch.empty_like(cnt)
         out[g.perm] = cnt
         return out
+
+    # ---- registration ----------------------------------------------------------------------------------------------------------
+    def bbox_centre(self):
+        """float64 numpy [3]: the centre of the cloud's bounding box (the point the registration sums are taken about)."""
+        if self._centre is None:
+            from .density import bbox_center
+            lo, hi, _ = bbox_center(self.xyz)
+            self._centre = 0.5 * (lo.double() + hi.double()).cpu().numpy()
+        return self._centre
+
+    def icp(self, source, max_correspondence_distance, **kwargs):
+        """``register.icp`` with this cloud as the target: one index serves many sources.  -> ``IcpResult``."""
+        from .register import icp
+        return icp(source, self, max_correspondence_distance, **kwargs)
 
 
 # ---- voxel downsampling ------------------------------------------------------------------------------------------------------------

@@ -30,33 +30,7 @@
 //      nearest written out), k_radius_count (nksr_radius_count: the 27 cells of a grid with cell >= radius).
 // Queries run in Morton order where they are the cloud itself: neighbouring lanes scan the same cells.
 #include "common.h"
-
-struct KnnGrid {
-    const float* xyz;          // [N,3] Morton-sorted points
-    const int32_t* start;      // [ncell] point range of every occupied cell
-    const int32_t* end;
-    const int64_t* hkeys;      // hash: cell key -> cell index
-    const int32_t* hvals;
-    int hcap;
-    float inv_cell;            // fp32 1 / cell size
-    float cell;
-};
-
-__device__ __forceinline__ void cell_of(const KnnGrid& g, const float q[3], int c[3]) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float p;
-        c[a] = half_index(q[a], g.inv_cell, p) >> 1;
-    }
-}
-
-// squared length with a FIXED rounding sequence: the bisection (count_within) and the later visits of the same candidates must
-// agree on every bit of it.  Left to the compiler (device code contracts a*b+c into fmas, and __fmul_rn / __fadd_rn are plain
-// operators in HIP) one inlined site fused and the other did not: a neighbour AT the k-th distance was counted but not visited
-// (2 - 10 % of the queries of k_sdf_from_points with large cells).  Explicit fmas cannot be re-associated.
-__device__ __forceinline__ float knn_d2(float ex, float ey, float ez) {
-    return fmaf(ez, ez, fmaf(ey, ey, ex * ex));
-}
+#include "knn_dev.h"
 
 // The (2R+1)^3 block of cells around cell c, walked in ONE order -- dx outer, dz inner, the points of a cell ascending -- and every
 // candidate p handed to f(index, ex, ey, ez, d2): e = q - p (the sign the estimators take it in), d2 = knn_d2(e).  The order is part
@@ -861,15 +835,6 @@ __global__ void __launch_bounds__(256) k_pyramid_level(const int64_t* __restrict
     pend[p] = cend[j - 1];
 }
 
-static KnnGrid make_grid(const float* xyz_sorted, const int32_t* start, const int32_t* end, const int64_t* hkeys,
-                         const int32_t* hvals, int hcap, float cell, float inv_cell) {
-    KnnGrid g;
-    g.xyz = xyz_sorted; g.start = start; g.end = end; g.hkeys = hkeys; g.hvals = hvals; g.hcap = hcap;
-    g.cell = cell;
-    g.inv_cell = inv_cell;   // the SAME fp32 reciprocal the host binned the points with
-    return g;
-}
-
 extern "C" int nksr_knn_pca_normals(const float* xyz_sorted, int64_t n, const int32_t* start, const int32_t* end,
                                     const int64_t* hkeys, const int32_t* hvals, int32_t hcap, float cell, float inv_cell, int k, int max_ring,
                                     float* normal_out, float* radius2_out, int32_t* valid_out, int32_t* todo_work, void* stream) {
@@ -1181,13 +1146,6 @@ extern "C" int nksr_knn_query_pyramid(const nksr_knn_pyramid_t* pyramid, int64_t
     KNN_PYR_DISPATCH(k_knn_query_pyramid, 33, k + (exclude_self ? 1 : 0), nq, P, query, nq, k, exclude_self, self_index, max_ring, idx_out, dist2_out,
                      valid_out);
     NKSR_CHECK_LAUNCH();
-    return NKSR_OK;
-}
-static int knn_grid_args(const char* who, const float* xyz_sorted, const int32_t* start, const int32_t* end, const int64_t* hkeys,
-                         const int32_t* hvals, int32_t hcap, float cell, float inv_cell) {
-    if (!xyz_sorted || !start || !end || !hkeys || !hvals) return nksr_set_error(NKSR_ERR_ARG, "%s: NULL grid arrays", who);
-    if (hcap < 8 || (hcap & (hcap - 1))) return nksr_set_error(NKSR_ERR_ARG, "%s: hcap must be a power of two >= 8 (got %d)", who, hcap);
-    if (!(cell > 0.f) || !(inv_cell > 0.f)) return nksr_set_error(NKSR_ERR_ARG, "%s: cell and inv_cell must be > 0", who);
     return NKSR_OK;
 }
 extern "C" int nksr_radius_count(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,
