@@ -683,6 +683,16 @@ int nksr_compact_scatter(const int32_t* flags, int64_t n, const int32_t* block_o
 int nksr_mise_constrain(const int64_t* vkeys_fine, int64_t nv, float* f_fine, const int64_t* chash_keys, const int32_t* chash_vals,
                         int32_t chash_cap, const float* f_coarse, const int64_t* ahash_keys, const int32_t* ahash_vals,
                         int32_t ahash_cap, void* stream);
+/* The same rule BEFORE the evaluation -- the replacement depends on the coarse level alone: f_fine [nv] receives the replaced values
+ * and only those, flag_out [nv] = 1 exactly where nksr_mise_constrain leaves the evaluated value in place (a cell centre, every
+ * adjacent coarse cell refined, a coarse vertex missing).  The field is then evaluated at the flagged vertices alone:
+ * nksr_gather_rows3_f32 of their positions, nksr_scatter_f32 of their values. */
+int nksr_mise_constrain_first(const int64_t* vkeys_fine, int64_t nv, float* f_fine, const int64_t* chash_keys, const int32_t* chash_vals,
+                              int32_t chash_cap, const float* f_coarse, const int64_t* ahash_keys, const int32_t* ahash_vals,
+                              int32_t ahash_cap, int32_t* flag_out, void* stream);
+/* dst [nsel, 3] = src [sel[i], 0..2];  dst [sel[i]] = src [i] -- sel: distinct int32 row indices */
+int nksr_gather_rows3_f32(const float* src, const int32_t* sel, int64_t nsel, float* dst, void* stream);
+int nksr_scatter_f32(const float* src, const int32_t* sel, int64_t nsel, float* dst, void* stream);
 /* children of the flagged cells: out has 8 keys per selected cell */
 int nksr_cell_children(const int64_t* cell_keys, const int32_t* sel, int64_t nsel, int64_t* child_keys, void* stream);
 /* triangle emission: edge keys (lower vertex index*3+axis) [ntri_total,3] */
@@ -691,6 +701,21 @@ int nksr_mc_emit(const int32_t* corner_idx, const int32_t* config, const int32_t
 /* mesh vertices from unique edge keys (vhash: nksr_hash_build table of vkeys) */
 int nksr_mc_vertices(const int64_t* edge_keys, int64_t nedge, const int64_t* vkeys, const int64_t* vhash_keys, const int32_t* vhash_vals,
                      int32_t vhash_cap, const float* vpos, const float* f, float h, float* verts_out, void* stream);
+/* The same mesh without the key stream.  The edge key of nksr_mc_emit, corner index * 3 + axis, is a slot p in [0, 3 nv); the id of an
+ * edge -- its rank among the sorted unique keys -- is the exclusive sum of used[] at p.
+ * Sequence: used [3 nv + 1] zeroed, nksr_mc_mark_edges, eid = nksr_exclusive_sum_i32 of used (its last entry = the number of edges),
+ * nksr_mc_faces, nksr_mc_edge_vertices.  3 nv < 2^31.
+ * mark: used[p] = 1 and far_out[p] = the corner index of the edge's far end for every edge a triangle names (far_out [3 nv], written
+ * where used; cells that share an edge store the same values: plain stores).
+ * faces_out [ntri_total, 3] int32 = eid at the positions nksr_mc_emit writes its keys.
+ * vertices: row eid[p] of verts_out [ne, 3], edge_vkey_out [ne] (lattice key of the lower end) and edge_axis_out [ne] for every used
+ * slot p < nslot = 3 nv, by the arithmetic of nksr_mc_vertices. */
+int nksr_mc_mark_edges(const int32_t* corner_idx, const int32_t* config, int64_t ncell, int32_t* used, int32_t* far_out, void* stream);
+int nksr_mc_faces(const int32_t* corner_idx, const int32_t* config, const int32_t* tri_offset, int64_t ncell, const int32_t* eid,
+                  int32_t* faces_out, void* stream);
+int nksr_mc_edge_vertices(const int32_t* used, const int32_t* eid, const int32_t* far_in, int64_t nslot, const int64_t* vkeys,
+                          const float* vpos, const float* f, float h, float* verts_out, int64_t* edge_vkey_out, int8_t* edge_axis_out,
+                          void* stream);
 
 /* ---- marching cubes on the ADAPTIVE dual graph: cells as large as their hierarchy level (field.extract_dual_mesh with
  * LayerField(dec_svh, adaptive_depth), reference models/nksr_net.py:132,214,284; specification: oracle/dual_adaptive.py) ----------

@@ -194,6 +194,80 @@ __global__ void k_mc_vertices(const int64_t* __restrict__ edge_keys, int64_t ned
     verts[i * 3 + 2] = p[2];
 }
 
+// ---- edge ids from a scan (the uniform lattice) ------------------------------------------------------
+// The key of k_mc_emit, corner_idx[lo] * 3 + axis, IS a position p in [0, 3 nv): the rank of an edge among the unique keys is the
+// exclusive sum of used[] at p, so the mesh vertices get their ids -- in the order of the sorted unique keys -- without a key
+// stream, sort, unique or hash.  mark -> scan (nksr_exclusive_sum_i32, its last entry = the number of edges) -> faces, vertices.
+// Several cells store the SAME values to a slot they share (the far end of an edge is one lattice vertex): plain stores, no atomics.
+__global__ void k_mc_mark_edges(const int32_t* __restrict__ corner_idx, const int32_t* __restrict__ config, int64_t ncell,
+                                int32_t* __restrict__ used, int32_t* __restrict__ far) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ncell) return;
+    const int cfg = config[i];
+    const int nt = MC_NTRI[cfg];
+    int mask = 0;                                        // (a cut edge is named by up to five triangles of the cell: stored once)
+    for (int t = 0; t < nt * 3; ++t) mask |= 1 << MC_TRI[cfg][t];
+    for (int e = 0; e < 12; ++e) {
+        if (!((mask >> e) & 1)) continue;
+        const int lo = MC_EDGE_LO[e], axis = MC_EDGE_AXIS[e];
+        const int64_t p = (int64_t)corner_idx[i * 8 + lo] * 3 + axis;
+        used[p] = 1;
+        far[p] = corner_idx[i * 8 + (lo | (4 >> axis))];
+    }
+}
+
+__global__ void k_mc_faces(const int32_t* __restrict__ corner_idx, const int32_t* __restrict__ config,
+                           const int32_t* __restrict__ tri_offset, int64_t ncell, const int32_t* __restrict__ eid,
+                           int32_t* __restrict__ faces) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ncell) return;
+    const int cfg = config[i];
+    const int nt = MC_NTRI[cfg];
+    int64_t o = (int64_t)tri_offset[i] * 3;
+    for (int t = 0; t < nt * 3; ++t) {
+        int e = MC_TRI[cfg][t];
+        faces[o + t] = eid[(int64_t)corner_idx[i * 8 + MC_EDGE_LO[e]] * 3 + MC_EDGE_AXIS[e]];
+    }
+}
+
+// (the arithmetic of k_mc_vertices; the far end comes from k_mc_mark_edges instead of a hash probe)
+__global__ void k_mc_edge_vertices(const int32_t* __restrict__ used, const int32_t* __restrict__ eid, const int32_t* __restrict__ far,
+                                   int64_t nslot, const int64_t* __restrict__ vkeys, const float* __restrict__ vpos,
+                                   const float* __restrict__ f, float h, float* __restrict__ verts, int64_t* __restrict__ edge_vkey,
+                                   int8_t* __restrict__ edge_axis) {
+    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nslot || !used[p]) return;
+    const int64_t i = eid[p];
+    int64_t v0 = p / 3;
+    int axis = (int)(p % 3);
+    const int v1 = far[p];
+    float f0 = f[v0], f1 = f[v1 >= 0 ? v1 : v0];
+    const float df = f0 - f1;
+    const float t = f0 / df;
+    float q[3] = {vpos[v0 * 3], vpos[v0 * 3 + 1], vpos[v0 * 3 + 2]};
+    const float th = t * h;                 // (rounded product, then rounded sum: contraction is off in this file)
+    q[axis] = q[axis] + th;
+    verts[i * 3] = q[0];
+    verts[i * 3 + 1] = q[1];
+    verts[i * 3 + 2] = q[2];
+    edge_vkey[i] = vkeys[v0];
+    edge_axis[i] = (int8_t)axis;
+}
+
+// ---- rows of 3 floats gathered by index, one float scattered by index (the evaluated subset of a MISE level) ----
+__global__ void k_gather_rows3(const float* __restrict__ src, const int32_t* __restrict__ sel, int64_t nsel, float* __restrict__ dst) {
+    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nsel * 3) return;
+    const int64_t r = t / 3;
+    dst[t] = src[(int64_t)sel[r] * 3 + (t - r * 3)];
+}
+
+__global__ void k_scatter_f32(const float* __restrict__ src, const int32_t* __restrict__ sel, int64_t nsel, float* __restrict__ dst) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nsel) return;
+    dst[sel[i]] = src[i];
+}
+
 #define LAUNCH1D(kern, n, stream, ...)                                                              \
     do {                                                                                            \
         if ((n) > 0) {                                                                              \
@@ -249,6 +323,31 @@ extern "C" int nksr_mc_vertices(const int64_t* edge_keys, int64_t nedge, const i
     LAUNCH1D(k_mc_vertices, nedge, stream, edge_keys, nedge, vkeys, vhash_keys, vhash_vals, vhash_cap, vpos, f, h, verts_out);
     return NKSR_OK;
 }
+extern "C" int nksr_mc_mark_edges(const int32_t* corner_idx, const int32_t* config, int64_t ncell, int32_t* used, int32_t* far_out,
+                                  void* stream) {
+    LAUNCH1D(k_mc_mark_edges, ncell, stream, corner_idx, config, ncell, used, far_out);
+    return NKSR_OK;
+}
+extern "C" int nksr_mc_faces(const int32_t* corner_idx, const int32_t* config, const int32_t* tri_offset, int64_t ncell, const int32_t* eid,
+                             int32_t* faces_out, void* stream) {
+    LAUNCH1D(k_mc_faces, ncell, stream, corner_idx, config, tri_offset, ncell, eid, faces_out);
+    return NKSR_OK;
+}
+extern "C" int nksr_mc_edge_vertices(const int32_t* used, const int32_t* eid, const int32_t* far_in, int64_t nslot, const int64_t* vkeys,
+                                     const float* vpos, const float* f, float h, float* verts_out, int64_t* edge_vkey_out,
+                                     int8_t* edge_axis_out, void* stream) {
+    if (nslot >= (1ll << 31)) return nksr_set_error(NKSR_ERR_ARG, "edge slots: 3 nv must stay below 2^31");
+    LAUNCH1D(k_mc_edge_vertices, nslot, stream, used, eid, far_in, nslot, vkeys, vpos, f, h, verts_out, edge_vkey_out, edge_axis_out);
+    return NKSR_OK;
+}
+extern "C" int nksr_gather_rows3_f32(const float* src, const int32_t* sel, int64_t nsel, float* dst, void* stream) {
+    LAUNCH1D(k_gather_rows3, nsel * 3, stream, src, sel, nsel, dst);
+    return NKSR_OK;
+}
+extern "C" int nksr_scatter_f32(const float* src, const int32_t* sel, int64_t nsel, float* dst, void* stream) {
+    LAUNCH1D(k_scatter_f32, nsel, stream, src, sel, nsel, dst);
+    return NKSR_OK;
+}
 
 // ---- MISE hanging-vertex constraint ------------------------------------------------------------------
 // A refined lattice vertex that sits on a coarse edge (one odd coordinate) or coarse face (two odd
@@ -256,21 +355,20 @@ extern "C" int nksr_mc_vertices(const int64_t* edge_keys, int64_t nedge, const i
 // value is then replaced by the mean of the coarse end points / face corners: an unrefined neighbour
 // has equal-sign corners, so no sign change can appear on the shared face and the refined mesh closes
 // against it (no T-junction cracks).
-__global__ void k_mise_constrain(const int64_t* __restrict__ vkeys_fine, int64_t nv, float* __restrict__ f_fine,
-                                 const int64_t* __restrict__ ch_keys, const int32_t* __restrict__ ch_vals, int ch_cap,
-                                 const float* __restrict__ f_coarse, const int64_t* __restrict__ ah_keys,
-                                 const int32_t* __restrict__ ah_vals, int ah_cap) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv) return;
+// The rule for one refined vertex: true and `out` = the value that replaces the evaluated one; false where the evaluated value
+// stays (a cell centre, every adjacent coarse cell refined, or a coarse vertex missing).  It depends on the coarse level alone.
+__device__ __forceinline__ bool mise_replacement(int64_t vkey_fine, const int64_t* __restrict__ ch_keys, const int32_t* __restrict__ ch_vals,
+                                                 int ch_cap, const float* __restrict__ f_coarse, const int64_t* __restrict__ ah_keys,
+                                                 const int32_t* __restrict__ ah_vals, int ah_cap, float& out) {
     int g[3];
-    morton_decode_biased(vkeys_fine[i], NKSR_BIAS0, g[0], g[1], g[2]);
+    morton_decode_biased(vkey_fine, NKSR_BIAS0, g[0], g[1], g[2]);
     const int odd[3] = {g[0] & 1, g[1] & 1, g[2] & 1};
     const int k = odd[0] + odd[1] + odd[2];
-    if (k == 3) return;
+    if (k == 3) return false;
     if (k == 0) {   // coincides with a coarse vertex: inherit its (possibly constrained) value
         const int j = hash_find(ch_keys, ch_vals, ch_cap, morton_biased(g[0] >> 1, g[1] >> 1, g[2] >> 1, NKSR_BIAS0));
-        if (j >= 0) f_fine[i] = f_coarse[j];
-        return;
+        if (j >= 0) out = f_coarse[j];
+        return j >= 0;
     }
     // coarse cells sharing the edge / face: along an ODD axis the cell is fixed ((g-1)/2), along an EVEN
     // axis both cells g/2 - 1 and g/2 touch it
@@ -285,7 +383,7 @@ __global__ void k_mise_constrain(const int64_t* __restrict__ vkeys_fine, int64_t
         for (int y = 0; y < cnt[1]; ++y)
             for (int z = 0; z < cnt[2]; ++z)
                 all_active = all_active && hash_find(ah_keys, ah_vals, ah_cap, morton_biased(lo[0] + x, lo[1] + y, lo[2] + z, NKSR_BIAS0)) >= 0;
-    if (all_active) return;
+    if (all_active) return false;
     // mean over the coarse vertices spanning the edge / face: odd axes take both (g-1)/2 and (g+1)/2
     float s = 0.f;
     int n = 0;
@@ -297,7 +395,39 @@ __global__ void k_mise_constrain(const int64_t* __restrict__ vkeys_fine, int64_t
                 const int j = hash_find(ch_keys, ch_vals, ch_cap, morton_biased(cx, cy, cz, NKSR_BIAS0));
                 if (j >= 0) { s += f_coarse[j]; ++n; }
             }
-    if (n == (1 << k)) f_fine[i] = s * (k == 1 ? 0.5f : 0.25f);
+    if (n == (1 << k)) out = s * (k == 1 ? 0.5f : 0.25f);
+    return n == (1 << k);
+}
+
+__global__ void k_mise_constrain(const int64_t* __restrict__ vkeys_fine, int64_t nv, float* __restrict__ f_fine,
+                                 const int64_t* __restrict__ ch_keys, const int32_t* __restrict__ ch_vals, int ch_cap,
+                                 const float* __restrict__ f_coarse, const int64_t* __restrict__ ah_keys,
+                                 const int32_t* __restrict__ ah_vals, int ah_cap) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    float v;
+    if (mise_replacement(vkeys_fine[i], ch_keys, ch_vals, ch_cap, f_coarse, ah_keys, ah_vals, ah_cap, v)) f_fine[i] = v;
+}
+
+// The same rule BEFORE the evaluation: the replaced values are written, flag = 1 marks the vertices that still need the field.
+__global__ void k_mise_constrain_first(const int64_t* __restrict__ vkeys_fine, int64_t nv, float* __restrict__ f_fine,
+                                       const int64_t* __restrict__ ch_keys, const int32_t* __restrict__ ch_vals, int ch_cap,
+                                       const float* __restrict__ f_coarse, const int64_t* __restrict__ ah_keys,
+                                       const int32_t* __restrict__ ah_vals, int ah_cap, int32_t* __restrict__ flag) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    float v;
+    const bool replaced = mise_replacement(vkeys_fine[i], ch_keys, ch_vals, ch_cap, f_coarse, ah_keys, ah_vals, ah_cap, v);
+    if (replaced) f_fine[i] = v;
+    flag[i] = replaced ? 0 : 1;
+}
+
+extern "C" int nksr_mise_constrain_first(const int64_t* vkeys_fine, int64_t nv, float* f_fine, const int64_t* chash_keys,
+                                         const int32_t* chash_vals, int32_t chash_cap, const float* f_coarse, const int64_t* ahash_keys,
+                                         const int32_t* ahash_vals, int32_t ahash_cap, int32_t* flag_out, void* stream) {
+    LAUNCH1D(k_mise_constrain_first, nv, stream, vkeys_fine, nv, f_fine, chash_keys, chash_vals, chash_cap, f_coarse, ahash_keys, ahash_vals,
+             ahash_cap, flag_out);
+    return NKSR_OK;
 }
 
 extern "C" int nksr_mise_constrain(const int64_t* vkeys_fine, int64_t nv, float* f_fine, const int64_t* chash_keys, const int32_t* chash_vals,

@@ -4,8 +4,9 @@ Mirrors ``field.extract_dual_mesh(mise_iter=0, grid_upsample=1, max_points=-1)``
 reference (call sites examples/recons_simple.py:27, recons_scannet.py:29,
 recons_colored_mesh.py:30, models/nksr_net.py:214,284) returning ``.v [V,3] f32``,
 ``.f [T,3] int``, ``.c [V,3]`` (NKSR-USAGE.md:52,79).  Steps:
-base dual cells -> (lattice vertices, f) -> MISE split of sign-changing cells -> 256-case
-table -> edge-keyed vertex dedup (radix sort + unique) -> mask trim -> world units.
+base dual cells -> (lattice vertices, f) -> MISE split of sign-changing cells (a refined level is constrained
+first and evaluated only where the value stays) -> 256-case table -> edge ids by a scan over the (vertex, axis)
+slots (the adaptive dual graph: radix sort + unique of the vertex names) -> mask trim -> world units.
 Host syncs happen only where a size (cells, vertices, triangles) must reach the host.
 """
 import os
@@ -124,11 +125,22 @@ def _extract(field, mise_iter, grid_upsample, max_points):
         nv, nc = vkeys.numel(), cells.numel()
         pos = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         call('nksr_lattice_positions', ptr(vkeys), nv, float(h), float(0.5 * w0), ptr(pos), stream())
-        f = field._evaluate_f_model(pos, False, max_points=batch).value
-        if prev is not None:   # hanging vertices take the coarse interpolant: no T-junction cracks
+        if prev is None:
+            f = field._evaluate_f_model(pos, False, max_points=batch).value
+        else:
+            # hanging vertices take the coarse interpolant (no T-junction cracks) and coincident ones the coarse value: both are
+            # known from the coarse level, so the constraint runs FIRST and the field is evaluated only where its value stays
             ch, ah = prev[0], prev[2]
-            call('nksr_mise_constrain', ptr(vkeys), nv, ptr(f), ptr(ch.hkeys), ptr(ch.hvals), ch.cap, ptr(prev[1]), ptr(ah.hkeys), ptr(ah.hvals),
-                 ah.cap, stream())
+            f = torch.empty(nv, dtype=torch.float32, device=dev)
+            need = torch.empty(nv, dtype=torch.int32, device=dev)
+            call('nksr_mise_constrain_first', ptr(vkeys), nv, ptr(f), ptr(ch.hkeys), ptr(ch.hvals), ch.cap, ptr(prev[1]), ptr(ah.hkeys),
+                 ptr(ah.hvals), ah.cap, ptr(need), stream())
+            sel = ops.compact(need)
+            if sel.numel():
+                ps = torch.empty((sel.numel(), 3), dtype=torch.float32, device=dev)
+                call('nksr_gather_rows3_f32', ptr(pos), ptr(sel), sel.numel(), ptr(ps), stream())
+                fs = field._evaluate_f_model(ps, False, max_points=batch).value.contiguous()
+                call('nksr_scatter_f32', ptr(fs), ptr(sel), sel.numel(), ptr(f), stream())
         config = torch.empty(nc, dtype=torch.int32, device=dev)
         ntri = torch.empty(nc + 1, dtype=torch.int32, device=dev)
         ntri[nc] = 0
@@ -155,17 +167,24 @@ def _extract(field, mise_iter, grid_upsample, max_points):
     T = int(tri_off[nc].item())
     if T == 0:
         return empty
-    ekeys = torch.empty(T * 3, dtype=torch.int64, device=dev)
-    call('nksr_mc_emit', ptr(cidx), ptr(config), ptr(tri_off), nc, ptr(ekeys), stream())
-    uek = ops.sort_unique(ops.dedup_keys(ekeys) if ekeys.numel() >= (1 << 19) else ekeys)      # every edge vertex is named by ~6 triangle corners
-    faces = ops.HashTable(uek).query(ekeys).view(T, 3)
-    ne = uek.numel()
+    # every mesh vertex sits on a lattice edge (lower end point v, axis): slot 3 v + axis.  vkeys is sorted, so the id of an edge
+    # -- its rank in (key of the lower end point, axis) order -- is the exclusive sum of the "used" marks at its slot
+    ns = 3 * nv
+    if ns >= (1 << 31) - 1:
+        raise RuntimeError('mesh lattice too large: %d vertices (3 per vertex edge slots must stay below 2^31)' % nv)
+    used = torch.zeros(ns + 1, dtype=torch.int32, device=dev)
+    far = torch.empty(ns, dtype=torch.int32, device=dev)
+    call('nksr_mc_mark_edges', ptr(cidx), ptr(config), nc, ptr(used), ptr(far), stream())
+    eid = ops.exclusive_sum_i32(used)
+    ne = int(eid[ns].item())
+    faces = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    call('nksr_mc_faces', ptr(cidx), ptr(config), ptr(tri_off), nc, ptr(eid), ptr(faces), stream())
+    # position and canonical identity of every mesh vertex: (lattice key of the lower end point, axis)
     verts = torch.empty((ne, 3), dtype=torch.float32, device=dev)
-    call('nksr_mc_vertices', ptr(uek), ne, ptr(vkeys), ptr(vhash.hkeys), ptr(vhash.hvals), vhash.cap, ptr(pos), ptr(f), float(h), ptr(verts), stream())
-
-    # canonical identity of every mesh vertex: (lattice key of the lower end point, axis)
-    ev = torch.div(uek, 3, rounding_mode='floor')
-    edge_vkey, edge_axis = vkeys[ev], (uek - ev * 3).to(torch.int8)
+    edge_vkey = torch.empty(ne, dtype=torch.int64, device=dev)
+    edge_axis = torch.empty(ne, dtype=torch.int8, device=dev)
+    call('nksr_mc_edge_vertices', ptr(used), ptr(eid), ptr(far), ns, ptr(vkeys), ptr(pos), ptr(f), float(h), ptr(verts), ptr(edge_vkey),
+         ptr(edge_axis), stream())
     verts, faces, (edge_vkey, edge_axis) = _trim(field, verts, faces, (edge_vkey, edge_axis), masked=True)
     res = _result(field, verts, faces)
     res.edge_vkey, res.edge_axis, res.lattice_h = edge_vkey, edge_axis, h
