@@ -528,7 +528,7 @@ int nksr_points_owner_flags(const nksr_chunk_grid_t* grid, const float* xyz, int
 int nksr_halo_band_flags(const int64_t* keys, const int32_t* ijk, int64_t n, const int64_t* klo, int32_t nchunk, const float* shift,
                          const float* tlo, const float* thi, float w, int32_t* seg_out, int32_t* flags_out, void* stream);
 
-/* ---- grid-hash nearest neighbours (csrc/knn.hip) ----------------------------------------------------
+/* ---- grid-hash nearest neighbours (csrc/knn_normals.hip, knn_sdf.hip, knn_query.hip) ----------------------------------------------------
  * Points Morton-sorted by a uniform grid of size `cell` (keys from nksr_point_keys with inv_w0 =
  * inv_cell); start/end = nksr_site_ranges of the occupied cells; hkeys/hvals = their hash. */
 /* kNN-PCA normals (unoriented): nksr.get_estimate_normal_preprocess_fn, examples/recons_waymo.py:36,

@@ -4,7 +4,7 @@ The input side of the tool-chain (``MeshEvaluator`` / ``MeshQuery`` / ``MeshTopo
 photogrammetry scan needs before ``Reconstructor.reconstruct`` -- thinning to a working density and dropping stray returns -- and
 the neighbour search the package already runs for its normals, its SDF ground truth and its metrics, with the indices handed out.
 
-  * ``CloudIndex(xyz)``: the Morton grid and octree of csrc/knn.hip (``neighbours.PointGrid`` / ``PointPyramid``) built once;
+  * ``CloudIndex(xyz)``: the Morton grid and octree of csrc/knn_query.hip (``neighbours.PointGrid`` / ``PointPyramid``) built once;
     ``.knn`` / ``.radius_count`` / ``.mean_knn_distance`` (kernels ``k_knn_query_pyramid``, ``k_radius_count``).
   * ``voxel_downsample``: one point per occupied voxel, the mean (or the input point nearest the mean) of every attribute
     (csrc/cloud.hip ``k_voxel_reduce``: fp64 sums in a fixed order, no atomics, bitwise repeatable).

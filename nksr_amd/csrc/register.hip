@@ -1,7 +1,7 @@
 // Rigid registration of point clouds (nksr_amd/register.py: cloud.icp): the pass an ICP iteration consists of.
 //
 //   k_icp_accumulate<METHOD>  nksr_icp_accumulate: one lane per source point -- transform (fp64), nearest target point within the radius
-//                             (the 27 cells of a PointGrid with cell >= radius, candidates four at a time like k_radius_count, fp32
+//                             (the 27 cells of a PointGrid with cell >= radius, knn_cells27 + knn_scan4 of knn_dev.h, fp32
 //                             knn_d2 decides, ties go to the lowest caller index), then the terms of the normal equations in fp64:
 //                             the moment sums of Kabsch (METHOD 0, point-to-point) or J J^T, J r of the linearised point-to-plane
 //                             error (METHOD 1).  One row of partial sums per workgroup.
@@ -102,21 +102,10 @@ __global__ void __launch_bounds__(NKSR_ICP_BLOCK) k_icp_accumulate(KnnGrid g, co
             auto consider = [&](int kk, float d2) {
                 if (d2 < bd || (d2 == bd && (best < 0 || perm[kk] < perm[best]))) { bd = d2; best = kk; }
             };
-            for (int j = 0; j < 27; ++j) {
-                const int ci = hash_find(g.hkeys, g.hvals, g.hcap, morton_biased(c[0] + j / 9 - 1, c[1] + (j / 3) % 3 - 1, c[2] + j % 3 - 1, NKSR_BIAS0));
-                if (ci < 0) continue;
-                const int e = g.end[ci];
-                int kk = g.start[ci];
-                for (; kk + 4 <= e; kk += 4) {
-                    float t[12];
-#pragma unroll
-                    for (int u = 0; u < 12; ++u) t[u] = g.xyz[(int64_t)kk * 3 + u];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) consider(kk + u, knn_d2(q[0] - t[3 * u], q[1] - t[3 * u + 1], q[2] - t[3 * u + 2]));
-                }
-                for (; kk < e; ++kk)
-                    consider(kk, knn_d2(q[0] - g.xyz[(int64_t)kk * 3], q[1] - g.xyz[(int64_t)kk * 3 + 1], q[2] - g.xyz[(int64_t)kk * 3 + 2]));
-            }
+            knn_cells27(g, c, [&](int ci) {
+                knn_scan4(g.xyz, g.start[ci], g.end[ci], q, consider);
+                return true;
+            });
         }
         corr[i] = best >= 0 ? perm[best] : (int64_t)-1;
         if (best >= 0) {

@@ -6,7 +6,7 @@ points (reference: ext/sdfgen/sdf_from_points.cu:142-235, bound in ext/sdfgen/bi
 The reference builds a CUDA kd-tree (tinyflann), writes the k indices of every query and runs one of two kernels over them.
 Here (nb_points <= 32): the reference cloud is binned once into a uniform grid (Morton sort + cell hash, ``neighbours.PointGrid``), an
 octree is stacked on it (``neighbours.PointPyramid``: the same sorted points, cells x2 per level), and ONE kernel per call
-(csrc/knn.hip ``k_sdf_pyramid``) takes every query to the scale at which the cloud is within one cell of it, keeps its k nearest
+(csrc/knn_sdf.hip ``k_sdf_pyramid``) takes every query to the scale at which the cloud is within one cell of it, keeps its k nearest
 candidates sorted in registers while it descends the cells around it with box pruning, and evaluates the estimator from them -- no
 index lists, no second pass.  What is left (queries farther from the cloud than 4 cells of the coarsest level; nb_points > 32,
 which bisects for the k-th distance instead) goes through single grids 4x coarser per round (``neighbours.search_every_scale``: the

@@ -78,7 +78,7 @@ class PCNNField(BaseField):
         return self.xyz.device
 
     def evaluate_color(self, xyz_world):
-        """Colour of the nearest input point (grid-hash nearest neighbour, csrc/knn.hip)."""
+        """Colour of the nearest input point (grid-hash nearest neighbour, csrc/knn_query.hip)."""
         from ..neighbours import PointGrid, choose_cell_size
         if getattr(self, '_grid', None) is None or self._grid.xyz.device != xyz_world.device:
             ref = self.xyz.to(xyz_world.device)

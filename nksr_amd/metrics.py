@@ -6,7 +6,7 @@ A mesh is scored against an oriented ground-truth cloud through area-uniform sam
   f-score       2 p r / (p + r), p = share of samples within t of the truth, r = share of the truth within t of a sample,
                 t = 0.01 ('f-score'), 0.015, 0.02 and 0.1 ('-outdoor')
 Every stage runs on the GPU (csrc/metrics.hip: face areas, the fp64 area CDF, the counter-based sampler, the fixed-order reduce;
-csrc/knn.hip: the exact nearest neighbour of every query over an octree of the other cloud).  Coordinates are recentred in float64
+its k_nn_metrics on the octree search of csrc/knn_topk_dev.h: the exact nearest neighbour of every query over an octree of the other cloud).  Coordinates are recentred in float64
 by the centre of the target's bounding box before they are rounded to float32, so scenes far from the origin keep their precision
 (nksr_amd/mesh_input.py, which turns every caller's array into a checked device tensor).
 Results are bitwise reproducible: the samples depend on (seed, index) only and no sum uses float atomics.

@@ -1,4 +1,5 @@
-"""Neighbour search over a point cloud (csrc/knn.hip): the Morton grid, the octree stacked on it, the cell size that suits a
+"""Neighbour search over a point cloud (csrc/knn_dev.h, knn_walk_dev.h, knn_topk_dev.h and the kernels on them: knn_normals.hip, knn_sdf.hip,
+knn_query.hip, metrics.hip): the Morton grid, the octree stacked on it, the cell size that suits a
 neighbourhood size, and the one loop that takes a search through every scale.  Used by the normals, ``ext.sdfgen``, the mesh metrics,
 ``cloud.CloudIndex`` and the colour field.
 """
@@ -10,7 +11,7 @@ from . import ops
 from ._lib import KNN_LEVELS, KnnPyramidT, call, ptr, stream
 from .svh import SparseGrid, inv_w0_f32
 
-MAX_K = 32              # csrc/knn.hip keeps the candidates of k <= 32 sorted in registers; more neighbours take the bisection kernels
+MAX_K = 32              # csrc/knn_topk_dev.h keeps the candidates of k <= 32 sorted in registers; more neighbours take the bisection kernels
 _RINGS = 4              # rings searched per grid when a search is retried on coarser cells
 _MAX_ROUNDS = 16        # the cell size grows 4x per round: 4^16 cells of the first size span any finite cloud
 
@@ -50,7 +51,7 @@ class PointGrid:
 
 class PointPyramid:
     """Octree over a ``PointGrid``: level l = cells of size cell * 2^l (keys = the grid's keys >> 3 l), each with its point range, the
-    range of its children on the level below and their octant mask, and a key hash (csrc/knn.hip ``KnnPyramid``).  Built upward from
+    range of its children on the level below and their octant mask, and a key hash (csrc/knn_topk_dev.h ``KnnPyramid``).  Built upward from
     the grid until a level has <= ``top_cells`` cells (one kernel + one hash per level; the level sizes come back to the host) or
     there are ``max_levels`` of them -- ``max_levels=1``: the grid alone, as the search kernels take it.
     Eight, not one: keys are biased coordinates, so the cells either side of a coordinate plane through the origin never merge."""

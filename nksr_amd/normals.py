@@ -1,4 +1,4 @@
-"""kNN-PCA normal estimation + sensor orientation on the GPU (csrc/knn.hip).
+"""kNN-PCA normal estimation + sensor orientation on the GPU (csrc/knn_normals.hip).
 
 Mirrors the recipe the reference ships in source form (examples/recons_waymo_cpu.py:21-41, the
 stand-in for ``nksr.get_estimate_normal_preprocess_fn(64, 85.0)``, examples/recons_waymo.py:36):

@@ -1,4 +1,4 @@
-"""Per-stage times of the point-cloud preprocessing (nksr_amd/cloud.py; csrc/cloud.hip, csrc/knn.hip).
+"""Per-stage times of the point-cloud preprocessing (nksr_amd/cloud.py; csrc/cloud.hip, csrc/knn_query.hip).
 
     python -m nksr_amd.tools.prof_cloud_ops [--sizes 1000000 10000000] [--voxel 0.1] [--reps 5] [--json OUT]
 

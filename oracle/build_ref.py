@@ -1,7 +1,7 @@
 """Builds the ONE piece of the reference that ships as source and touches this path's "next" rows: the training ground-truth
 generator ``ext.sdfgen.sdf_from_points`` (/root/reference/ext/sdfgen/{bind.cpp,sdf_from_points.cu} + ext/common/kdtree_cuda.cu,
 cutil_math.h), compiled FROM THE REFERENCE'S OWN SOURCES as a PyTorch-ROCm extension for gfx950.  TEST INFRASTRUCTURE: the result
-``oracle/_ref/nksr_sdfgen.so`` is loaded only by tests/test_gpu_sdfgen.py, to check csrc/knn.hip's k_sdf_from_points and the
+``oracle/_ref/nksr_sdfgen.so`` is loaded only by tests/test_gpu_sdfgen.py, to check csrc/knn_sdf.hip's k_sdf_from_points and the
 restatement oracle/sdfgen.py against the reference's OWN kernels (kd-tree kNN + estimator) on the GPU box.
 
     python -m oracle.build_ref [-v]       (in the dev container: needs /root/reference; hipcc cross-compiles without a GPU, ~90 s)

@@ -1,4 +1,4 @@
-"""ext.sdfgen.sdf_from_points -- ours (csrc/knn.hip: one octree-kNN kernel) against the REFERENCE'S OWN extension (oracle/_ref/nksr_sdfgen.so:
+"""ext.sdfgen.sdf_from_points -- ours (csrc/knn_sdf.hip: one octree-kNN kernel) against the REFERENCE'S OWN extension (oracle/_ref/nksr_sdfgen.so:
 kd-tree build + kNN + estimator, compiled from /root/reference/ext by oracle/build_ref.py) on the same MI355X, same inputs: the one
 operation of this project whose reference implementation runs here.  TEST infrastructure (it lives under tests/ because it loads oracle/_ref).
 python tests/sdfgen_vs_ref.py [--variants] [--breakdown]"""

@@ -1,5 +1,5 @@
 """nksr_amd/cloud.py on the GPU against tests/cloud_ref.py (numpy / scipy cKDTree, float64): k nearest neighbours, radius counts, the
-outlier masks, voxel downsampling (csrc/knn.hip k_knn_query_*, k_radius_count; csrc/cloud.hip k_voxel_reduce) and the preprocess_fn
+outlier masks, voxel downsampling (csrc/knn_query.hip k_knn_query_*, k_radius_count; csrc/cloud.hip k_voxel_reduce) and the preprocess_fn
 plumbing.  The standard input, cloud A: 20 000 noisy sphere samples + 1 000 uniform stray points (cloud_ref.cloud_a).
 
 Tolerances.  Distances: the kernels take fp32 differences of fp32 coordinates (<= 6e-8 relative each) and sum their squares in fp32,

@@ -1,4 +1,4 @@
-"""GPU kNN kernels (csrc/knn.hip): kNN-PCA normals + sensor orientation (the preprocess_fn of
+"""GPU kNN kernels (csrc/knn_normals.hip, knn_query.hip): kNN-PCA normals + sensor orientation (the preprocess_fn of
 examples/recons_waymo_cpu.py:21-41) and the nearest-neighbour colour field (PCNNField,
 examples/recons_colored_mesh.py:28) against scipy cKDTree / numpy."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""MeshEvaluator on the MI355X (nksr_amd/metrics.py, csrc/metrics.hip, the 1-NN epilogue of csrc/knn.hip) against numpy / cKDTree
+"""MeshEvaluator on the MI355X (nksr_amd/metrics.py, csrc/metrics.hip, its k_nn_metrics on the octree search of csrc/knn_topk_dev.h) against numpy / cKDTree
 restatements and the CPU oracle (oracle/metrics.py)."""
 import time
 

@@ -97,7 +97,7 @@ def test_sdf_from_points_matches_the_reference_binary(case):
 
 @pytest.mark.parametrize('k', [8, 20])
 def test_octree_search_equals_the_single_grid_rounds_and_hands_on_what_it_cannot_reach(k, monkeypatch):
-    """The default search (every scale in one launch, csrc/knn.hip k_sdf_pyramid) against the single-grid rounds it replaced and
+    """The default search (every scale in one launch, csrc/knn_sdf.hip k_sdf_pyramid) against the single-grid rounds it replaced and
     against exact kNN -- with queries at every distance: in the band, across the bounding box, and 100 cloud diameters away
     (beyond the coarsest level: those come back unanswered and take the rounds)."""
     from oracle import sdfgen as osdf
@@ -125,7 +125,7 @@ def test_octree_search_equals_the_single_grid_rounds_and_hands_on_what_it_cannot
 
 @pytest.mark.parametrize('imls', [False, True])
 def test_more_neighbours_than_the_register_list_take_the_bisection_kernels(imls):
-    """nb_points = 40 > 32: the any-k path (csrc/knn.hip k_sdf_from_points on plain grids, coarser per round) against the oracle, at the
+    """nb_points = 40 > 32: the any-k path (csrc/knn_sdf.hip k_sdf_from_points on plain grids, coarser per round) against the oracle, at the
     caps of the tests above.  Queries on two shells 0.15 either side of the surface (every one of the 40 neighbours votes the same
     sign) and 30 at 100 cloud diameters, which only the coarse rounds reach."""
     from oracle import sdfgen as osdf
@@ -154,7 +154,7 @@ def test_more_neighbours_than_the_register_list_take_the_bisection_kernels(imls)
 
 @pytest.mark.parametrize('k', [8, 20])
 def test_bisection_kernels_equal_the_register_list_kernels_on_the_same_grid(k):
-    """csrc/knn.hip k_knn_mean_dist / k_sdf_from_points (any k: bisection for the k-th distance, the estimators fed in scan order)
+    """csrc/knn_sdf.hip k_knn_mean_dist / k_sdf_from_points (any k: bisection for the k-th distance, the estimators fed in scan order)
     against k_knn_mean_dist_pyramid / k_sdf_pyramid (k <= 32: sorted register list, nearest first) on ONE grid, 4 rings.  Both take
     their squared distances from the same fixed fma chain, so the neighbour sets and the summed terms are the same bits: what is
     left is the order of summation.  (An fp64 kd-tree finds no query of these inputs whose k-th and (k+1)-th neighbours, or two
