@@ -636,6 +636,40 @@ int nksr_icp_accumulate(const float* xyz_sorted, int64_t n_ref, const int32_t* s
                         int64_t* corr_out, double* partials_out, void* stream);
 int nksr_icp_reduce(const double* partials, int64_t nrows, double* sums_out, void* stream);
 
+/* ---- point-cloud segmentation (csrc/segment.hip; nksr_amd/segment.py: cloud.cluster_dbscan, cloud.segment_plane) ----------------
+ * DBSCAN on a grid as nksr_radius_count takes it (cell >= radius; n < 2^31 points in the grid's order).  j is a neighbour of i iff
+ * knn_d2(x_j - x_i) <= fl32(radius)^2, the predicate of nksr_radius_count; core [n] (uint8) = the points with at least min_points
+ * neighbours, themselves included: (nksr_radius_count(cap = min_points, exclude_self = 0) >= min_points).
+ * nksr_dbscan_components: union-find over the pairs of core points that are neighbours.  parent_out [n] = the smallest sorted index of
+ *   the point's component (-1 for a point that is not core), root_flags_out [n + 1] = (parent_out[i] == i), then a 0.
+ * nksr_dbscan_min_caller: min_index_out [n]: at every root r the smallest perm [n] (int64: the grid's order -> the caller's) over the
+ *   points with parent[i] == r; 0x7F7F7F7F elsewhere.  Integer atomicMin: independent of the order the lanes run in.
+ * nksr_dbscan_border: label [n] holds the labels of the core points on entry (anything at the others); on return every point that is
+ *   not core holds the smallest label among the core points that are its neighbours, or -1 without one.
+ * Plane RANSAC.  xyz [n, 3] fp32 in the caller's order; a plane is (a, b, c, d) in fp64; the residual of a point is
+ * s = ((a x + b y) + c z) + d in fp64 with every product and sum rounded on its own; inlier iff |s| <= threshold (finite, >= 0).
+ * nksr_plane_score: counts_out [n_planes] (int32) = the inliers of every plane of planes [n_planes, 4] (device); -1 for a plane that
+ *   is not finite or has a = b = c = 0.  Integer atomics only.
+ * nksr_plane_moments: plane [4], centre [3] (device).  mask_out [n] (uint8) = inlier; partials_out [ceil(n / NKSR_ICP_BLOCK),
+ *   NKSR_ICP_FIELDS] = per workgroup the fp64 sums over its inliers, x' = x - centre: [NKSR_PLANE_COUNT] the count, [NKSR_PLANE_SUM + a]
+ *   sum x'_a, [NKSR_PLANE_MOMENT + k] sum x'_a x'_b over a <= b, row after row (xx, xy, xz, yy, yz, zz), zeros behind; fixed order, no
+ *   atomics: the rows go to nksr_icp_reduce. */
+#define NKSR_PLANE_COUNT 0
+#define NKSR_PLANE_SUM 1
+#define NKSR_PLANE_MOMENT 4
+#define NKSR_PLANE_FIELDS 10
+int nksr_dbscan_components(const float* xyz_sorted, int64_t n, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                           const int32_t* hvals, int32_t hcap, float cell, float inv_cell, float radius, const uint8_t* core,
+                           int32_t* parent_out, int32_t* root_flags_out, void* stream);
+int nksr_dbscan_min_caller(const int32_t* parent, const int64_t* perm, int64_t n, int32_t* min_index_out, void* stream);
+int nksr_dbscan_border(const float* xyz_sorted, int64_t n, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                       const int32_t* hvals, int32_t hcap, float cell, float inv_cell, float radius, const uint8_t* core, int32_t* label,
+                       void* stream);
+int nksr_plane_score(const float* xyz, int64_t n, const double* planes, int64_t n_planes, double threshold, int32_t* counts_out,
+                     void* stream);
+int nksr_plane_moments(const float* xyz, int64_t n, const double* plane, const double* centre, double threshold, uint8_t* mask_out,
+                       double* partials_out, void* stream);
+
 /* ---- voxel reduction of a point cloud (csrc/cloud.hip; nksr_amd/cloud.py voxel_downsample) -----------------------------------
  * order [n] = point indices sorted by voxel key, start / end [n_vox] = the run of every voxel in it (nksr_run_table_u64 of the sorted
  * keys: start_out without its last entry, and without its first). mean_xyz_out [n_vox, 3] and mean_attr_out [n_vox, C] = the mean of xyz [n, 3] and of attr [n, C] (C = 0: attr and

@@ -4,7 +4,8 @@ Exports the surface of the reference's ``nksr`` package that its examples and tr
 use: ``Reconstructor``, ``NKSRNetwork``, ``SparseFeatureHierarchy``,
 ``get_estimate_normal_preprocess_fn`` and the sub-modules ``fields``, ``svh``, ``configs``,
 ``utils``; beyond it the mesh and point-cloud tools (``metrics``, ``MeshTopology``, ``MeshGeometry``, ``MeshSimplifier``, ``MeshSlicer``, ``MeshBoundary``, ``cloud`` -- neighbour queries, voxel downsampling, outlier masks, normal
-orientation and rigid registration (``cloud.icp`` / ``icp_multiscale`` / ``evaluate_registration`` / ``apply_transform``) -- and the
+orientation, rigid registration (``cloud.icp`` / ``icp_multiscale`` / ``evaluate_registration`` / ``apply_transform``) and
+segmentation (``cloud.cluster_dbscan`` / ``segment_plane``) -- and the
 ``preprocess_fn`` makers on it).  ``import nksr`` resolves to this package through the top-level ``nksr`` shim.
 """
 from . import cloud, configs, fields, metrics, svh, utils
@@ -14,12 +15,14 @@ from .mesh_simplify import MeshSimplifier
 from .mesh_slice import MeshSlicer
 from .mesh_topology import MeshTopology
 from .nn.network import NKSRNetwork
-from .preprocess import (compose_preprocess_fns, get_estimate_normal_preprocess_fn, get_estimate_oriented_normal_preprocess_fn,
-                         get_radius_outlier_preprocess_fn, get_statistical_outlier_preprocess_fn, get_voxel_downsample_preprocess_fn)
+from .preprocess import (compose_preprocess_fns, get_dbscan_preprocess_fn, get_estimate_normal_preprocess_fn,
+                         get_estimate_oriented_normal_preprocess_fn, get_radius_outlier_preprocess_fn, get_remove_plane_preprocess_fn,
+                         get_statistical_outlier_preprocess_fn, get_voxel_downsample_preprocess_fn)
 from .reconstructor import Reconstructor
 from .svh import SparseFeatureHierarchy
 
 __all__ = ['Reconstructor', 'NKSRNetwork', 'SparseFeatureHierarchy', 'get_estimate_normal_preprocess_fn', 'MeshTopology', 'MeshGeometry', 'MeshSimplifier',
            'MeshSlicer', 'MeshBoundary', 'get_voxel_downsample_preprocess_fn', 'get_radius_outlier_preprocess_fn', 'get_statistical_outlier_preprocess_fn',
-           'get_estimate_oriented_normal_preprocess_fn', 'compose_preprocess_fns', 'fields', 'svh', 'configs', 'utils', 'metrics', 'cloud']
+           'get_estimate_oriented_normal_preprocess_fn', 'get_dbscan_preprocess_fn', 'get_remove_plane_preprocess_fn', 'compose_preprocess_fns',
+           'fields', 'svh', 'configs', 'utils', 'metrics', 'cloud']
 __version__ = '0.1.0'

@@ -13,6 +13,8 @@ the neighbour search the package already runs for its normals, its SDF ground tr
     that has positions only -- signs propagated along the minimum spanning forest of the kNN graph.
   * ``icp`` / ``icp_multiscale`` / ``evaluate_registration`` / ``apply_transform`` / ``IcpResult`` (nksr_amd/register.py,
     csrc/register.hip): rigid registration of one cloud onto another, point-to-point or point-to-plane, before scans are merged.
+  * ``cluster_dbscan`` / ``segment_plane`` / ``plane_scores`` / ``sample_planes`` / ``DbscanResult`` (nksr_amd/segment.py,
+    csrc/segment.hip): a scene split into its objects -- density-based clusters, and the dominant plane found by RANSAC.
 ``nksr_amd.preprocess`` wraps them as ``preprocess_fn`` for ``Reconstructor.reconstruct``.  GPU tensors only.
 """
 import torch
@@ -22,6 +24,7 @@ from ._lib import call, ptr, require_gpu, stream
 from .neighbours import MAX_K, _RINGS, PointGrid, PointPyramid, _grid_args, choose_cell_size, search_every_scale
 from .orient import OrientedNormals, estimate_normals, orient_graph, orient_normals  # noqa: F401  (part of this module's surface)
 from .register import IcpResult, apply_transform, evaluate_registration, icp, icp_multiscale  # noqa: F401  (part of this module's surface)
+from .segment import DbscanResult, cluster_dbscan, plane_scores, sample_planes, segment_plane  # noqa: F401  (part of this module's surface)
 from .svh import inv_w0_f32
 
 
@@ -176,6 +179,12 @@ class CloudIndex:
         out = torch.empty_like(cnt)
         out[g.perm] = cnt
         return out
+
+    # ---- clusters --------------------------------------------------------------------------------------------------------------
+    def cluster_dbscan(self, eps, min_points):
+        """``segment.cluster_dbscan`` on this index (the grid of ``radius_count(eps)``) -> ``DbscanResult``."""
+        from .segment import dbscan_on_index
+        return dbscan_on_index(self, eps, min_points)
 
     # ---- registration ----------------------------------------------------------------------------------------------------------
     def bbox_centre(self):

@@ -2,12 +2,14 @@
 //   k_topo_keys         three (edge key, half-edge id) pairs per face; validity of faces, referenced vertices
 //   (the runs of the sorted keys: nksr_run_counts_u64 / nksr_run_table_u64 of csrc/prims.hip, keys from the sentinel on in no run)
 //   k_topo_edge_classes edge_v, incident faces, class, the face across every manifold half-edge, totals
-//   k_uf_*              union-find over a node and pair list: hook (atomicCAS, larger root under smaller), flatten, dense labels
+//   k_uf_*              union-find over a node and pair list: hook (atomicCAS, larger root under smaller), flatten, dense labels (uf_dev.h)
 //   k_topo_*            labels of the other kind of node, per-component counts and boxes, compaction
 // Every kernel is one lane per item, latency- and atomic-bound; no sum here is a floating-point one.
 #include "common.h"
 #include "mesh_dev.h"
+#include "uf_dev.h"
 #include "wave_dev.h"
+static_assert(UF_BLOCK == MESH_BLOCK, "the union-find kernels are launched with MESH_LAUNCH here");
 
 // the key no edge has and that sorts behind every edge of a mesh of nv vertices, inside the 32 + bit_length(nv) sorted bits
 __device__ __forceinline__ uint64_t tp_sentinel(int64_t nv) { return ((uint64_t)nv << 32) | (uint64_t)nv; }
@@ -99,74 +101,14 @@ __global__ void k_topo_finish_totals(const uint32_t* __restrict__ edge_start, in
     totals[4] = (n_half - (ne > 0 || n_half > 0 ? (int64_t)edge_start[ne] : 0)) / 3;
 }
 
-// ---- 4. union-find ---------------------------------------------------------------------------------------------------------------
-// DETERMINISM.  A hook only ever points a ROOT at a smaller node of a set it is being joined with (atomicCAS(parent[hi], hi, lo),
-// lo < hi), and path halving only replaces a parent by an ancestor.  So at every moment parent[x] <= x, parent[x] lies in the set of
-// x, and the smallest node of a set can never receive a parent: whatever order the lanes ran in, once every pair has been hooked each
-// tree's root is the MINIMUM NODE INDEX of its component, and the flatten pass (parent[x] = root of x) leaves an array that is a
-// function of the graph alone.  Dense ids are the ranks of the roots, so ascending id follows ascending minimum node index.
-// A lane may read a stale parent (another CU's L1): every value a parent ever held is an ancestor, so a stale read costs steps, and
-// the CAS decides on the word's current value.
-__device__ __forceinline__ int32_t uf_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void uf_store(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int32_t uf_find(int32_t* parent, int32_t x) {
-    int32_t cur = uf_load(parent + x);
-    while (cur != x) {
-        const int32_t next = uf_load(parent + cur);
-        if (next == cur) return cur;
-        uf_store(parent + x, next);                     // path halving: x skips its parent
-        x = cur;
-        cur = next;
-    }
-    return cur;
-}
-
-__global__ void __launch_bounds__(MESH_BLOCK) k_uf_init(int32_t* __restrict__ parent, int64_t n, const uint8_t* __restrict__ valid) {
-    const int64_t i = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
-    if (i < n) parent[i] = !valid || valid[i] ? (int32_t)i : -1;
-}
-
+// ---- 4. union-find (the device functions, the determinism argument and k_uf_init / k_uf_flatten / k_uf_labels: uf_dev.h) -------------
 __global__ void __launch_bounds__(MESH_BLOCK) k_uf_hook(int32_t* parent, int64_t n, const int32_t* __restrict__ pairs, int64_t m) {
     const int64_t i = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
     if (i >= m) return;
-    int32_t a = pairs[i * 2], b = pairs[i * 2 + 1];
+    const int32_t a = pairs[i * 2], b = pairs[i * 2 + 1];
     if (a < 0 || b < 0 || a >= n || b >= n || a == b) return;
     if (parent[a] < 0 || parent[b] < 0) return;         // (a node outside the graph: -1 is written before the hooks and never changes)
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const int32_t old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) return;
-        a = old;                                        // hi was no root any more: go on from what it points to
-        b = lo;
-    }
-}
-
-__global__ void __launch_bounds__(MESH_BLOCK) k_uf_flatten(int32_t* parent, int64_t n, int32_t* __restrict__ root_flags) {
-    const int64_t i = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    int32_t r = uf_load(parent + i);
-    if (r >= 0) {
-        while (true) {
-            const int32_t p = uf_load(parent + r);
-            if (p == r) break;
-            r = p;
-        }
-        if (r != (int32_t)i) uf_store(parent + i, r);   // (a root keeps pointing at itself: other lanes end their walk on it)
-    }
-    root_flags[i] = r == (int32_t)i ? 1 : 0;
-    if (i == 0) root_flags[n] = 0;
-}
-
-__global__ void __launch_bounds__(MESH_BLOCK) k_uf_labels(const int32_t* __restrict__ parent, int64_t n, const int32_t* __restrict__ root_rank,
-                                                          int32_t* __restrict__ label) {
-    const int64_t i = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int32_t r = parent[i];
-    label[i] = r >= 0 ? root_rank[r] : -1;
+    uf_hook(parent, a, b);
 }
 
 // the faces round an edge, linked in a chain: pair i = (face of sorted half-edge i, face of half-edge i + 1) inside a run, else (-1, -1)

@@ -15,17 +15,12 @@
 // restatement in plain fp64 arithmetic gets every term to the last bit, and differs from the sums by the summation order alone.
 #include "common.h"
 #include "knn_dev.h"
+#include "wave_dev.h"
 
 #define ICP_WAVES (NKSR_ICP_BLOCK / NKSR_WAVE)
 static_assert(NKSR_ICP_BLOCK % NKSR_WAVE == 0 && NKSR_ICP_FIELDS <= NKSR_ICP_BLOCK, "whole wavefronts, one lane per field at the end");
 static_assert(NKSR_ICP_PT_PQ + 9 <= NKSR_ICP_FIELDS && NKSR_ICP_PL_JJ + 21 == NKSR_ICP_PL_JR && NKSR_ICP_PL_JR + 6 == NKSR_ICP_PL_RR &&
               NKSR_ICP_PL_RR < NKSR_ICP_FIELDS, "layout of the sums");
-
-__device__ __forceinline__ double icp_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // p = R s + t, every product and sum rounded on its own
 __device__ __forceinline__ void icp_transform(const double* __restrict__ T, const float s[3], double p[3]) {
@@ -118,7 +113,7 @@ __global__ void __launch_bounds__(NKSR_ICP_BLOCK) k_icp_accumulate(KnnGrid g, co
     const int wave = threadIdx.x / NKSR_WAVE, lane = threadIdx.x % NKSR_WAVE;
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
-        const double v = icp_wave_sum(term[f]);
+        const double v = wave_sum_f64(term[f]);
         if (lane == 0) s_red[wave][f] = v;
     }
     __syncthreads();

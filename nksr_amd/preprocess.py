@@ -5,9 +5,9 @@
 examples/recons_waymo.py:36, gis_app.py:41; CPU recipe examples/recons_waymo_cpu.py:21-41):
 kNN-PCA normals, flipped towards the sensor, grazing (> deg) points dropped.
 
-The cleaning steps in front of it (nksr_amd/cloud.py): voxel downsampling and the two outlier filters, chained with
-``compose_preprocess_fns``.  The filters keep the input order of the points they keep; the downsampler returns its voxels in
-ascending key order."""
+The cleaning steps in front of it (nksr_amd/cloud.py): voxel downsampling, the two outlier filters, plane removal and DBSCAN
+cluster selection, chained with ``compose_preprocess_fns``.  The filters keep the input order of the points they keep; the
+downsampler returns its voxels in ascending key order."""
 
 
 def get_estimate_normal_preprocess_fn(knn=64, deg=85.0):
@@ -59,6 +59,30 @@ def get_statistical_outlier_preprocess_fn(k=16, std_ratio=2.0):
     def fn(xyz, normal, sensor):
         from .cloud import statistical_outlier_mask
         return _select(statistical_outlier_mask(xyz, k, std_ratio), xyz, normal, sensor)
+    return fn
+
+
+def get_dbscan_preprocess_fn(eps, min_points, min_cluster_size=None, keep_largest=None):
+    """Keeps the points of the ``cloud.cluster_dbscan(eps, min_points)`` clusters with at least ``min_cluster_size`` points and / or of
+    the ``keep_largest`` largest clusters (ties on size go to the lower label); noise is dropped, the input order is kept.  Clusters
+    are a property of the WHOLE cloud: under ``reconstruct(..., chunk_size > 0)`` this function would run per chunk, where an object cut
+    by a chunk boundary counts as two smaller ones -- call ``cloud.cluster_dbscan`` on the whole cloud first and pass what it keeps."""
+    def fn(xyz, normal, sensor):
+        from .cloud import cluster_dbscan
+        r = cluster_dbscan(xyz, eps, min_points)
+        return _select(r.point_mask(r.select(min_cluster_size, keep_largest)), xyz, normal, sensor)
+    return fn
+
+
+def get_remove_plane_preprocess_fn(distance_threshold, num_iterations=1000, seed=0):
+    """Drops the inliers of the dominant plane (``cloud.segment_plane``: ground, floor, table); the input order is kept."""
+    def fn(xyz, normal, sensor):
+        import torch
+        from .cloud import segment_plane
+        _, inliers = segment_plane(xyz, distance_threshold, num_iterations=num_iterations, seed=seed)
+        keep = torch.ones(xyz.shape[0], dtype=torch.bool, device=xyz.device)
+        keep[inliers] = False
+        return _select(keep, xyz, normal, sensor)
     return fn
 
 

@@ -27,11 +27,11 @@ import time
 import numpy as np
 
 
-def kernel_resources():
-    """{kernel: {VGPRs, VGPRs Spill, SGPRs Spill, ScratchSize, Occupancy, LDS Size}} as hipcc reports them for csrc/register.hip"""
+def kernel_resources(source='register.hip'):
+    """{kernel: {VGPRs, VGPRs Spill, SGPRs Spill, ScratchSize, Occupancy, LDS Size}} as hipcc reports them for csrc/<source>"""
     from nksr_amd import build
     cmd = [build.HIPCC] + build.FLAGS + ['-Rpass-analysis=kernel-resource-usage', '--cuda-device-only', '-c',
-                                         os.path.join(build.CSRC, 'register.hip'), '-o', os.devnull]
+                                         os.path.join(build.CSRC, source), '-o', os.devnull]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError('hipcc failed:\n%s' % r.stderr)
@@ -43,11 +43,11 @@ def kernel_resources():
             continue
         if m.group(1) == 'Function Name':
             name = m.group(2)
-            mm = re.match(r'_Z(\d+)', name)                   # Itanium mangling: length-prefixed name, ILi<k>E = template argument k
+            mm = re.match(r'_ZL?(\d+)', name)                 # Itanium mangling: length-prefixed name, ILi<k>E / ILb<k>E = template argument k
             if mm:
                 rest = name[mm.end():]
                 n = int(mm.group(1))
-                t = re.match(r'ILi(\d+)E', rest[n:])
+                t = re.match(r'IL[ib](\d+)E', rest[n:])
                 name = rest[:n] + ('<%s>' % t.group(1) if t else '')
             out[name] = {}
         elif name:
