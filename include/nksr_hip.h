@@ -138,6 +138,12 @@ int nksr_point_mlp(const float* xyz, const float* feat, int64_t n, float inv_w0,
 int nksr_splat_mean(const float* xyz_sorted, const float* feat_sorted, int C, const int32_t* start,
                     const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* out,
                     void* stream);
+/* The point encoder's two splats onto one level in ONE pass over the points: voxel_feat [n, 32] = nksr_splat_mean of the 32-channel
+ * feat_sorted, and -- normal_sorted [N, 3] != NULL -- normal_sum [n, 3], weight_sum [n] = nksr_splat_trilinear of normal_sorted on the
+ * same level, each bit for bit.  normal_sorted: optional (NULL: normal_sum / weight_sum are not touched and may be NULL). */
+int nksr_splat_encode(const float* xyz_sorted, const float* feat_sorted, const float* normal_sorted, const int32_t* start,
+                      const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* voxel_feat,
+                      float* normal_sum, float* weight_sum, void* stream);
 /* 3x3x3 submanifold sparse convolution on the fp32 matrix cores: out = act(b + sum_s W[s]^T in[nbr[:,s]]
  * (+ residual)),  W [27, C, C]  in / W: 16-byte aligned (NKSR_ERR_ARG otherwise); bias / residual: optional (NULL). */
 int nksr_sparse_conv3(const float* in, const int32_t* nbr, int32_t n, int C, const float* W, const float* bias,

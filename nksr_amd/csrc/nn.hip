@@ -1,6 +1,7 @@
 // Sparse feature-hierarchy network kernels (network.encoder / network.unet; reference call sites
 // models/nksr_net.py:73-78, hyper-parameters configs/default/train.yaml:17-18 "unet.f_maps: 32").
 //   k_point_mlp      per-point 2-layer MLP on (local cell coordinate, orientation feature)
+//   k_splat_encode32 the encoder's one pass over the points: 32-channel splat-mean + the splat of the input normals
 //   k_sparse_conv3   3x3x3 submanifold sparse convolution, gather-GEMM on the fp32 matrix cores
 //   k_pool_children  mean of the (Morton-contiguous) children of every coarse voxel
 //   k_gather_rows    feature transfer between hierarchies / parent -> child up-sampling
@@ -134,6 +135,49 @@ __global__ void __launch_bounds__(256) k_splat_mean32(const float* __restrict__ 
         for (int i = 0; i < 4; ++i) { wsum += wq[i]; acc = fmaf(wq[i], f[i], acc); }
     });
     if (live) out[(int64_t)j * 32 + s] = acc * (wsum > 0.f ? 1.f / wsum : 0.f);
+}
+
+// The encoder's pass over the points, once for both of its splats: the 32-channel mean of k_splat_mean32 and -- nrm != NULL -- the
+// 3-channel weighted SUM of the input normals with its weight sum, as k_splat_trilinear (hierarchy.hip) forms them on the same grid.
+// Both kernels list the same points with the same weights in the same order (xyz, inv_w, cell ranges and neighbour rows are the
+// same); only what is read per listed point differs, so one listing serves both.  Every lane sums its feature channel in fp32 in
+// list order (the bits of k_splat_mean32); lanes s < 3 also sum their normal channel in fp64 and round once at the end (the bits of
+// k_splat_trilinear: lane 0 carries the weight sum).  Four listed points per trip, as both of them: 58 VGPRs, 8 waves per SIMD.  More
+// rows in flight per wavefront cost more than they gave (HISTORY.md: 8 or 16 points per trip and a prefetch of the next round's
+// candidates need 72-128 VGPRs, 7-4 waves per SIMD; 6.9 ms became 7.4-11.0).
+__global__ void __launch_bounds__(256) k_splat_encode32(const float* __restrict__ xyz, const float* __restrict__ feat,
+                                                        const float* __restrict__ nrm, const int32_t* __restrict__ start,
+                                                        const int32_t* __restrict__ end, const int32_t* __restrict__ nbr,
+                                                        const int32_t* __restrict__ ijk, int n, float inv_w, float* __restrict__ out,
+                                                        float* __restrict__ nsum_out, float* __restrict__ wsum_out) {
+    __shared__ int lk[8][SPLAT_LIST];
+    __shared__ float lw[8][SPLAT_LIST];
+    const int j = (blockIdx.x * 256 + threadIdx.x) >> 5, s = threadIdx.x & 31, h = threadIdx.x >> 5;
+    const bool live = j < n;                                         // (a dead half-wave walks an empty list next to its partner)
+    const int jc = live ? j : n - 1;
+    const float cx = (float)ijk[jc * 3] + 0.5f, cy = (float)ijk[jc * 3 + 1] + 0.5f, cz = (float)ijk[jc * 3 + 2] + 0.5f;
+    const int c = (live && s < 27) ? nbr[(int64_t)jc * 27 + s] : -1;
+    const bool nl = nrm != nullptr && s < 3;                         // this lane sums a normal channel
+    float acc = 0.f, wsum = 0.f;
+    double nacc = 0.0, nwsum = 0.0;
+    splat_for_each_point(xyz, start, end, c, cx, cy, cz, inv_w, s, lk[h], lw[h], [&](const int (&kq)[4], const float (&wq)[4]) {
+        float f[4], g[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f[i] = feat[(int64_t)kq[i] * 32 + s];
+        if (nl) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) g[i] = nrm[(int64_t)kq[i] * 3 + s];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { wsum += wq[i]; acc = fmaf(wq[i], f[i], acc); }
+        if (nl) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { nwsum += (double)wq[i]; nacc = fma((double)wq[i], (double)g[i], nacc); }
+        }
+    });
+    if (live) out[(int64_t)j * 32 + s] = acc * (wsum > 0.f ? 1.f / wsum : 0.f);
+    if (live && nl) nsum_out[(int64_t)j * 3 + s] = (float)nacc;
+    if (live && nl && s == 0) wsum_out[j] = (float)nwsum;
 }
 
 // ---- UDF mask branch (NeuralField, models/nksr_net.py:124-130) -------------------------------------------------
@@ -442,6 +486,17 @@ extern "C" int nksr_pool_children(const float* child_feat, const int32_t* start,
     if (n_parent <= 0) return NKSR_OK;
     if (!child_feat || !start || !end || !out) return nksr_set_error(NKSR_ERR_ARG, "pool_children: NULL arrays");
     LAUNCH1D(k_pool_children, (int64_t)n_parent * C, stream, child_feat, start, end, n_parent, C, out);
+    return NKSR_OK;
+}
+extern "C" int nksr_splat_encode(const float* xyz_sorted, const float* feat_sorted, const float* normal_sorted, const int32_t* start,
+                                 const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* voxel_feat,
+                                 float* normal_sum, float* weight_sum, void* stream) {
+    if (n <= 0) return NKSR_OK;
+    if (!xyz_sorted || !feat_sorted || !start || !end || !nbr || !ijk || !voxel_feat) return nksr_set_error(NKSR_ERR_ARG, "splat_encode: NULL arrays");
+    if (normal_sorted && (!normal_sum || !weight_sum)) return nksr_set_error(NKSR_ERR_ARG, "splat_encode: NULL normal_sum / weight_sum with normals given");
+    hipLaunchKernelGGL(k_splat_encode32, dim3(nksr_blocks((int64_t)n * 32, 256)), dim3(256), 0, (hipStream_t)stream, xyz_sorted, feat_sorted,
+                       normal_sorted, start, end, nbr, ijk, n, inv_w, voxel_feat, normal_sum, weight_sum);
+    NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
 extern "C" int nksr_gather_rows(const float* src, const int32_t* idx, int64_t n, int C, const float* add, float* out,

@@ -79,6 +79,7 @@ class EncodedCloud:
 
     def __init__(self):
         self.xyz = self.feat = self.keys = self.voxel_feat = None
+        self.normal_splat = None      # (grid, depth, normal_sum, weight_sum) of the encoder's grid, where its pass formed them
 
 
 # ---- thin wrappers over csrc/nn.hip ---------------------------------------------------------------------
@@ -121,6 +122,24 @@ def splat_mean(grid, d, inv_w0, site_keys, xyz_sorted, feat_sorted):
     call('nksr_splat_mean', ptr(xyz_sorted), ptr(feat_sorted), C_, ptr(st), ptr(en), ptr(grid.nbr), ptr(grid.ijk), n,
          float(inv_w0 * 2.0 ** (-d)), ptr(out), stream())
     return out
+
+
+def splat_encode(grid, d, inv_w0, site_keys, xyz_sorted, feat_sorted, normal_sorted=None):
+    """One pass over the points for both splats of the encoder: ``splat_mean`` of the 32-channel ``feat_sorted`` and -- with
+    ``normal_sorted`` [N, 3] -- ``splat_trilinear`` of it on the same grid: (voxel_feat, normal_sum or None, weight_sum or None)."""
+    n, dev = grid.num_voxels, grid.device
+    new = torch.zeros if xyz_sorted.shape[0] == 0 else torch.empty      # (as splat_trilinear: no launch on an empty cloud, zeros)
+    out = new((n, feat_sorted.shape[1]), dtype=torch.float32, device=dev)
+    ns = new((n, 3), dtype=torch.float32, device=dev) if normal_sorted is not None else None
+    ws = new(n, dtype=torch.float32, device=dev) if normal_sorted is not None else None
+    if xyz_sorted.shape[0] == 0:
+        return out, ns, ws
+    if feat_sorted.shape[1] != 32 or (normal_sorted is not None and normal_sorted.shape[1] != 3):
+        raise RuntimeError('splat_encode takes 32 feature channels and 3 normal channels')
+    st, en = site_ranges(site_keys, grid, d)
+    call('nksr_splat_encode', ptr(xyz_sorted), ptr(feat_sorted), ptr(normal_sorted), ptr(st), ptr(en), ptr(grid.nbr), ptr(grid.ijk), n,
+         float(inv_w0 * 2.0 ** (-d)), ptr(out), ptr(ns), ptr(ws), stream())
+    return out, ns, ws
 
 
 def splat_plane(grid, d, inv_w0, site_keys, xyz_sorted, normal_sorted):
@@ -205,7 +224,14 @@ class PointEncoder(nn.Module):
         g = torch.empty((n, self.channels), dtype=torch.float32, device=enc.xyz.device)
         call('nksr_point_mlp', ptr(enc.xyz), ptr(enc.feat), n, svh.inv_w0, self.channels, ptr(self.W1.detach().contiguous()),
              ptr(self.b1.detach().contiguous()), ptr(self.W2.detach().contiguous()), ptr(self.b2.detach().contiguous()), ptr(g), stream())
-        return splat_mean(svh.level(depth), depth, svh.inv_w0, enc.keys, enc.xyz, g)
+        grid = svh.level(depth)
+        if self.channels != 32 or enc.feat.shape[1] != 3:
+            return splat_mean(grid, depth, svh.inv_w0, enc.keys, enc.xyz, g)
+        # the splat of the input normals (the U-Net's normal target) lists the same points with the same weights: formed in the same
+        # pass, on the encoder's grid, and kept for StructureUNet
+        vf, ns, ws = splat_encode(grid, depth, svh.inv_w0, enc.keys, enc.xyz, g, enc.feat)
+        enc.normal_splat = (grid, depth, ns, ws)
+        return vf
 
 
 class StructureUNet(nn.Module):
@@ -266,6 +292,7 @@ class StructureUNet(nn.Module):
             SparseFeatureHierarchy(enc_svh.voxel_size, D, dev).build_point_neighborhood_sorted(enc.keys, getattr(enc, 'cells', None))
         feat = FeatureSet(D)
         dec_levels = [None] * D
+        je_levels = [None] * D               # candidate voxel -> encoder voxel, of the levels whose candidates all stayed
         y_up, keep_up = None, None           # trunk features / "continue" flags of the level above
         for d in range(D - 1, -1, -1):
             gc = cand.level(d)
@@ -290,6 +317,8 @@ class StructureUNet(nn.Module):
             if not bool(exist.all()):          # prune "not-exist" voxels (needs a re-indexed grid)
                 y, s, status = y[exist].contiguous(), s[exist].contiguous(), status[exist]
                 gc = SparseGrid(keys[exist].contiguous(), d, enc_svh.voxel_size, coarse=dec_levels[d + 1] if d < D - 1 else None)
+            elif gc is cand.level(d):
+                je_levels[d] = je
             dec_levels[d] = gc
             feat.structure_features[d] = s
             feat.trunk_features[d] = y
@@ -311,10 +340,18 @@ class StructureUNet(nn.Module):
                     feat.udf_features[d] = pl + self.udf_heads[d](y)
                 # splat on the CANDIDATE grid (it holds every cell that contains a point; the gather
                 # form of the splat walks neighbour voxels), then keep the rows of surviving voxels
-                s, ws = splat_trilinear(cand.level(d), d, enc_svh.inv_w0, enc.keys, enc.xyz, enc.feat)
-                if dec_levels[d] is not cand.level(d):
-                    sel = cand.level(d).hash.query(dec_levels[d].keys)
-                    s, ws = gather_rows(s, sel), ws[sel.long()]
+                stash = getattr(enc, 'normal_splat', None)
+                if stash is not None and gt_decoder_svh is None and stash[1] == d and stash[0] is enc_svh.level(d):
+                    # The encoder's pass formed this splat on ITS grid already.  The candidate grid is the 27-neighbourhood of the cells
+                    # that hold points; a voxel of it that the encoder grid has lists the same points in the same order there, and one
+                    # it lacks is beyond every point's 8 nearest centres, where every weight is 0: rows by index.
+                    je = je_levels[d] if je_levels[d] is not None else enc_svh.level(d).hash.query(dec_levels[d].keys)
+                    s, ws = gather_rows(stash[2], je), gather_rows(stash[3].view(-1, 1), je).view(-1)
+                else:
+                    s, ws = splat_trilinear(cand.level(d), d, enc_svh.inv_w0, enc.keys, enc.xyz, enc.feat)
+                    if dec_levels[d] is not cand.level(d):
+                        sel = cand.level(d).hash.query(dec_levels[d].keys)
+                        s, ws = gather_rows(s, sel), ws[sel.long()]
                 nv = s + self.normal_heads[d](y)
                 # unit length -- unless the splatted normals cancel (|sum w n| < 1e-2 sum w: both sides of a thin sheet in one voxel)
                 # or the voxel is barely touched (sum w < 1e-3: a point on the edge of its stencil weighs 0 or 1e-8 depending on
