@@ -117,6 +117,7 @@ int nksr_build_nbr_from_parent(const int32_t* ijk, const int64_t* keys, int32_t 
 int nksr_site_ranges(const int64_t* site_keys, int64_t ns, const int64_t* vox_keys, int32_t n, int level,
                      int32_t* start_out, int32_t* end_out, void* stream);
 
+/* ---- trilinear splats (csrc/splat.hip: this one, nksr_splat_mean, nksr_splat_encode, nksr_splat_plane) ---- */
 /* Trilinear splat (weighted sum + weight sum) of per-point features onto the voxels of one
  * level; points must be Morton-sorted with start/end = nksr_site_ranges of that level.
  * Point encoder skip path (network.encoder, models/nksr_net.py:73).
@@ -127,7 +128,7 @@ int nksr_splat_trilinear(const float* xyz_sorted, const float* feat_sorted, int 
                          float* out, float* wsum_out, void* stream);
 
 /* ---- sparse feature-hierarchy network (network.encoder / network.unet, models/nksr_net.py:73-78;
- *      csrc/nn.hip).  C = unet.f_maps = 32 (configs/default/train.yaml:17-18).
+ *      csrc/nn.hip; the splats: csrc/splat.hip).  C = unet.f_maps = 32 (configs/default/train.yaml:17-18).
  *      Every entry below checks its arguments before any launch: with n > 0 a NULL array is NKSR_ERR_ARG (a NULL pointer would pass
  *      the 16-byte alignment tests); the optional ones are named.  n <= 0 is NKSR_OK and touches nothing. --------------------- */
 /* per-point MLP on [local cell coordinate - 1/2 (3), orientation feature (3)]:  W1 [C,6], W2 [C,C] */

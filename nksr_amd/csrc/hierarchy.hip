@@ -1,12 +1,9 @@
-// Sparse voxel hierarchy: key generation, hash build/query, 27-neighbour tables, site ranges.
+// Sparse voxel hierarchy: key generation and coding, hash build/query, 27-neighbour tables, site ranges and sorted lookups,
+// footprint keys (plain and deduplicated per workgroup range), bounding box of a cloud.
 // Serves SparseFeatureHierarchy.build_point_splatting / grids[d] (reference call sites
 // models/nksr_net.py:57-62, models/loss.py:33-46).  All kernels are HBM-bound integer work:
 // one thread per element, coalesced key streams, hash probes served from L2.
-#include "common.h"
-// The oracle rounds every fp32 product before it is used (numpy).  Device code contracts a * b + c into one fma by default --
-// x * inv_w - centre then keeps the unrounded product, the trilinear weights move by an ulp of p and a splat whose normals nearly
-// cancel amplifies that to 1e-4 in the unit target (measured in round 3) -- so contraction is off in this file; explicit fmaf stays.
-#pragma clang fp contract(off)
+#include "launch.h"
 
 __global__ void k_splat_keys(const float* __restrict__ xyz, int64_t n, float inv_w0, int level, int mode,
                              int64_t* __restrict__ out) {
@@ -197,14 +194,6 @@ __global__ void __launch_bounds__(256) k_rank_sorted(const int64_t* __restrict__
     if (i < nq) out[i] = (int32_t)bound_i64(sorted, win[0], win[1], q[i], upper != 0);
 }
 
-#define LAUNCH1D(kern, n, stream, ...)                                                              \
-    do {                                                                                            \
-        if ((n) > 0) {                                                                              \
-            hipLaunchKernelGGL(kern, dim3(nksr_blocks((n), 256)), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__); \
-            NKSR_CHECK_LAUNCH();                                                                    \
-        }                                                                                           \
-    } while (0)
-
 extern "C" int nksr_splat_keys(const float* xyz, int64_t n, float inv_w0, int level, int mode, int64_t* keys_out,
                                void* stream) {
     if (level < 0 || level >= NKSR_MAX_DEPTH || (mode != 0 && mode != 1)) return nksr_set_error(NKSR_ERR_ARG, "bad level/mode");
@@ -275,61 +264,6 @@ extern "C" int nksr_rank_sorted(const int64_t* sorted, int64_t n, const int64_t*
 extern "C" int nksr_sorted_lookup(const int64_t* sorted, int64_t n, const int64_t* q, int64_t nq, int32_t* idx_out,
                                   void* stream) {
     LAUNCH1D(k_sorted_lookup, nq, stream, sorted, n, q, nq, idx_out);
-    return NKSR_OK;
-}
-
-// ---- trilinear splat-mean of per-point features onto the voxels of one level ------------------
-// Gather form (deterministic, no float atomics): voxel j visits the points of its 27 neighbour
-// cells (contiguous ranges of the Morton-sorted cloud) and weights them with the hat function
-// prod_a max(0, 1 - |x_a/w - (j_a + 1/2)|).  Used by the point encoder (network.encoder,
-// reference call site models/nksr_net.py:73) for the input-normal skip path.
-// One 32-lane half-wave per voxel, lane = neighbour cell: the 27 chains cell -> point range -> coordinates -> features run side by
-// side (a thread per voxel walked them one after the other: latency-bound, 0.68 ms at 7.8e5 voxels), then one fixed-tree sum per
-// channel over the lanes.
-__device__ __forceinline__ double half_sum_d(double p) {      // sum over the 32 lanes of this half-wave, fixed tree
-    p += __shfl_xor(p, 16, 32);
-    p += __shfl_xor(p, 8, 32);
-    p += __shfl_xor(p, 4, 32);
-    p += __shfl_xor(p, 2, 32);
-    p += __shfl_xor(p, 1, 32);
-    return p;
-}
-__global__ void __launch_bounds__(256) k_splat_trilinear(const float* __restrict__ xyz, const float* __restrict__ feat, int C,
-                                                         const int32_t* __restrict__ start, const int32_t* __restrict__ end,
-                                                         const int32_t* __restrict__ nbr, const int32_t* __restrict__ ijk, int n,
-                                                         float inv_w, float* __restrict__ out, float* __restrict__ wsum_out) {
-    __shared__ int lk[8][SPLAT_LIST];
-    __shared__ float lw[8][SPLAT_LIST];
-    const int j = (blockIdx.x * 256 + threadIdx.x) >> 5, s = threadIdx.x & 31, h = threadIdx.x >> 5;
-    const bool live = j < n;
-    const int jc = live ? j : n - 1;
-    // fp64 accumulators: the splat of the input normals is normalised afterwards, and where the normals of a voxel's points nearly
-    // cancel (both sides of a thin sheet) fp32 sums left 1e-4 of noise in the unit target (round 3: sites with |sum w n| ~ 0.1 sum w
-    // differed by 7e-5 from the fp64 oracle); the products w * f are exact in fp64, so only the order of the additions is left.
-    // The points that weigh at the voxel are listed first (common.h: splat_for_each_point, lane = neighbour cell), then lane =
-    // channel sums them in list order.
-    double acc = 0.0, wsum = 0.0;
-    const float cx = (float)ijk[jc * 3] + 0.5f, cy = (float)ijk[jc * 3 + 1] + 0.5f, cz = (float)ijk[jc * 3 + 2] + 0.5f;
-    const int c = (live && s < 27) ? nbr[(int64_t)jc * 27 + s] : -1;
-    const int ch = s < C ? s : 0;
-    splat_for_each_point(xyz, start, end, c, cx, cy, cz, inv_w, s, lk[h], lw[h], [&](const int (&kq)[4], const float (&wq)[4]) {
-        float f[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f[i] = feat[(int64_t)kq[i] * C + ch];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { wsum += (double)wq[i]; acc = fma((double)wq[i], (double)f[i], acc); }
-    });
-    if (live && s < C) out[(int64_t)j * C + s] = (float)acc;
-    if (live && s == 0) wsum_out[j] = (float)wsum;
-}
-
-extern "C" int nksr_splat_trilinear(const float* xyz_sorted, const float* feat_sorted, int C, const int32_t* start,
-                                    const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w,
-                                    float* out, float* wsum_out, void* stream) {
-    if (C < 1 || C > 8) return nksr_set_error(NKSR_ERR_ARG, "splat supports 1..8 channels");
-    if (n <= 0) return NKSR_OK;
-    if (!xyz_sorted || !feat_sorted || !start || !end || !nbr || !ijk || !out || !wsum_out) return nksr_set_error(NKSR_ERR_ARG, "splat_trilinear: NULL arrays");
-    LAUNCH1D(k_splat_trilinear, (int64_t)n * 32, stream, xyz_sorted, feat_sorted, C, start, end, nbr, ijk, n, inv_w, out, wsum_out);
     return NKSR_OK;
 }
 

@@ -5,7 +5,7 @@
 //   x = g*h + w0/2,  h = w0/(U 2^m),  lattice keys = Morton(g + 2^20).
 // Compaction is ordered (deterministic): per-wave ballot + popcount prefix inside a block,
 // block offsets from an exclusive scan.
-#include "common.h"
+#include "launch.h"
 // The oracle rounds every fp32 product before it is used (numpy).  Device code contracts a * b + c into one fma by default --
 // x * inv_w - centre then keeps the unrounded product, the trilinear weights move by an ulp of p and a splat whose normals nearly
 // cancel amplifies that to 1e-4 in the unit target (measured in round 3) -- so contraction is off in this file; explicit fmaf stays.
@@ -267,14 +267,6 @@ __global__ void k_scatter_f32(const float* __restrict__ src, const int32_t* __re
     if (i >= nsel) return;
     dst[sel[i]] = src[i];
 }
-
-#define LAUNCH1D(kern, n, stream, ...)                                                              \
-    do {                                                                                            \
-        if ((n) > 0) {                                                                              \
-            hipLaunchKernelGGL(kern, dim3(nksr_blocks((n), 256)), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__); \
-            NKSR_CHECK_LAUNCH();                                                                    \
-        }                                                                                           \
-    } while (0)
 
 extern "C" int nksr_base_cell_flags(const int32_t* nbr, int32_t n, int32_t* flags, void* stream) {
     LAUNCH1D(k_base_cell_flags, (int64_t)n, stream, nbr, n, flags);

@@ -1,19 +1,20 @@
 // Sparse feature-hierarchy network kernels (network.encoder / network.unet; reference call sites
 // models/nksr_net.py:73-78, hyper-parameters configs/default/train.yaml:17-18 "unet.f_maps: 32").
 //   k_point_mlp      per-point 2-layer MLP on (local cell coordinate, orientation feature)
-//   k_splat_encode32 the encoder's one pass over the points: 32-channel splat-mean + the splat of the input normals
 //   k_sparse_conv3   3x3x3 submanifold sparse convolution, gather-GEMM on the fp32 matrix cores
 //   k_pool_children  mean of the (Morton-contiguous) children of every coarse voxel
 //   k_gather_rows    feature transfer between hierarchies / parent -> child up-sampling
 //   k_linear         per-voxel linear heads (structure / basis / normal / udf)
+//   k_udf_decode     unsigned distance to the plane features of the UDF branch
+// (the encoder's splat-mean, the splat of the input normals and the plane features themselves: splat.hip)
 // The convolution is the only GEMM-shaped piece of the hot path: one wavefront owns a tile of 32
 // output voxels x 32 output channels and issues, per tap, 16 v_mfma_f32_32x32x2_f32 (exact fp32,
 // bitwise an fmaf chain) on a 32x32 gathered input tile staged in LDS; the 4 KiB tap weights are
 // read straight from L2/L1 (every wavefront reads the same tile).
-#include "common.h"
-// The oracle rounds every fp32 product before it is used (numpy).  Device code contracts a * b + c into one fma by default --
-// x * inv_w - centre then keeps the unrounded product, the trilinear weights move by an ulp of p and a splat whose normals nearly
-// cancel amplifies that to 1e-4 in the unit target (measured in round 3) -- so contraction is off in this file; explicit fmaf stays.
+#include "launch.h"
+// The oracle rounds every fp32 product before it is used (numpy) and device code contracts a * b + c into one fma by default, so
+// contraction is off in this file too (k_udf_decode forms trilinear weights; what an unrounded product costs: splat.hip); explicit
+// fmaf stays.
 #pragma clang fp contract(off)
 
 #define NN_C 32
@@ -75,146 +76,8 @@ __global__ void __launch_bounds__(256) k_point_mlp(const float* __restrict__ xyz
     }
 }
 
-// ---- trilinear splat-mean of C-channel point features (C <= 32) onto one level ------------------------------
-// one thread per (voxel, 8-channel group); gather form as k_splat_trilinear (hierarchy.hip)
-__global__ void k_splat_mean_c(const float* __restrict__ xyz, const float* __restrict__ feat, int C,
-                               const int32_t* __restrict__ start, const int32_t* __restrict__ end,
-                               const int32_t* __restrict__ nbr, const int32_t* __restrict__ ijk, int n, float inv_w,
-                               float* __restrict__ out) {
-    const int groups = (C + 7) / 8;
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (int64_t)n * groups) return;
-    const int j = (int)(t / groups), g = (int)(t % groups);
-    const int c0 = g * 8, nc = (C - c0) < 8 ? (C - c0) : 8;
-    float acc[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) acc[c] = 0.f;
-    float wsum = 0.f;
-    const float cx = (float)ijk[j * 3] + 0.5f, cy = (float)ijk[j * 3 + 1] + 0.5f, cz = (float)ijk[j * 3 + 2] + 0.5f;
-    for (int s = 0; s < 27; ++s) {
-        int c = nbr[(int64_t)j * 27 + s];
-        if (c < 0) continue;
-        for (int k = start[c]; k < end[c]; ++k) {
-            float wx = 1.f - fabsf(__fmul_rn(xyz[(int64_t)k * 3], inv_w) - cx);
-            float wy = 1.f - fabsf(__fmul_rn(xyz[(int64_t)k * 3 + 1], inv_w) - cy);
-            float wz = 1.f - fabsf(__fmul_rn(xyz[(int64_t)k * 3 + 2], inv_w) - cz);
-            if (wx <= 0.f || wy <= 0.f || wz <= 0.f) continue;
-            float w = wx * wy * wz;
-            wsum += w;
-            const float* f = feat + (int64_t)k * C + c0;
-#pragma unroll
-            for (int c2 = 0; c2 < 8; ++c2)
-                if (c2 < nc) acc[c2] = fmaf(w, f[c2], acc[c2]);
-        }
-    }
-    const float inv = wsum > 0.f ? 1.f / wsum : 0.f;
-    for (int c2 = 0; c2 < nc; ++c2) out[(int64_t)j * C + c0 + c2] = acc[c2] * inv;
-}
-
-// C = 32 specialisation: one 32-lane half-wave per voxel.  The points that weigh at the voxel are listed first (common.h:
-// splat_for_each_point, lane = neighbour cell), then lane = CHANNEL: four points per trip, each feature row one coalesced 128-byte
-// read of the half-wave; the sum runs over the points in list order (cell after cell), the same in every lane -- no reduction
-// over the lanes, one coalesced 128-byte store per voxel.
-__global__ void __launch_bounds__(256) k_splat_mean32(const float* __restrict__ xyz, const float* __restrict__ feat,
-                                                      const int32_t* __restrict__ start, const int32_t* __restrict__ end,
-                                                      const int32_t* __restrict__ nbr, const int32_t* __restrict__ ijk, int n,
-                                                      float inv_w, float* __restrict__ out) {
-    __shared__ int lk[8][SPLAT_LIST];
-    __shared__ float lw[8][SPLAT_LIST];
-    const int j = (blockIdx.x * 256 + threadIdx.x) >> 5, s = threadIdx.x & 31, h = threadIdx.x >> 5;
-    const bool live = j < n;                                         // (a dead half-wave walks an empty list next to its partner)
-    const int jc = live ? j : n - 1;
-    const float cx = (float)ijk[jc * 3] + 0.5f, cy = (float)ijk[jc * 3 + 1] + 0.5f, cz = (float)ijk[jc * 3 + 2] + 0.5f;
-    const int c = (live && s < 27) ? nbr[(int64_t)jc * 27 + s] : -1;
-    float acc = 0.f, wsum = 0.f;
-    splat_for_each_point(xyz, start, end, c, cx, cy, cz, inv_w, s, lk[h], lw[h], [&](const int (&kq)[4], const float (&wq)[4]) {
-        float f[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f[i] = feat[(int64_t)kq[i] * 32 + s];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { wsum += wq[i]; acc = fmaf(wq[i], f[i], acc); }
-    });
-    if (live) out[(int64_t)j * 32 + s] = acc * (wsum > 0.f ? 1.f / wsum : 0.f);
-}
-
-// The encoder's pass over the points, once for both of its splats: the 32-channel mean of k_splat_mean32 and -- nrm != NULL -- the
-// 3-channel weighted SUM of the input normals with its weight sum, as k_splat_trilinear (hierarchy.hip) forms them on the same grid.
-// Both kernels list the same points with the same weights in the same order (xyz, inv_w, cell ranges and neighbour rows are the
-// same); only what is read per listed point differs, so one listing serves both.  Every lane sums its feature channel in fp32 in
-// list order (the bits of k_splat_mean32); lanes s < 3 also sum their normal channel in fp64 and round once at the end (the bits of
-// k_splat_trilinear: lane 0 carries the weight sum).  Four listed points per trip, as both of them: 58 VGPRs, 8 waves per SIMD.  More
-// rows in flight per wavefront cost more than they gave (HISTORY.md: 8 or 16 points per trip and a prefetch of the next round's
-// candidates need 72-128 VGPRs, 7-4 waves per SIMD; 6.9 ms became 7.4-11.0).
-__global__ void __launch_bounds__(256) k_splat_encode32(const float* __restrict__ xyz, const float* __restrict__ feat,
-                                                        const float* __restrict__ nrm, const int32_t* __restrict__ start,
-                                                        const int32_t* __restrict__ end, const int32_t* __restrict__ nbr,
-                                                        const int32_t* __restrict__ ijk, int n, float inv_w, float* __restrict__ out,
-                                                        float* __restrict__ nsum_out, float* __restrict__ wsum_out) {
-    __shared__ int lk[8][SPLAT_LIST];
-    __shared__ float lw[8][SPLAT_LIST];
-    const int j = (blockIdx.x * 256 + threadIdx.x) >> 5, s = threadIdx.x & 31, h = threadIdx.x >> 5;
-    const bool live = j < n;                                         // (a dead half-wave walks an empty list next to its partner)
-    const int jc = live ? j : n - 1;
-    const float cx = (float)ijk[jc * 3] + 0.5f, cy = (float)ijk[jc * 3 + 1] + 0.5f, cz = (float)ijk[jc * 3 + 2] + 0.5f;
-    const int c = (live && s < 27) ? nbr[(int64_t)jc * 27 + s] : -1;
-    const bool nl = nrm != nullptr && s < 3;                         // this lane sums a normal channel
-    float acc = 0.f, wsum = 0.f;
-    double nacc = 0.0, nwsum = 0.0;
-    splat_for_each_point(xyz, start, end, c, cx, cy, cz, inv_w, s, lk[h], lw[h], [&](const int (&kq)[4], const float (&wq)[4]) {
-        float f[4], g[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f[i] = feat[(int64_t)kq[i] * 32 + s];
-        if (nl) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) g[i] = nrm[(int64_t)kq[i] * 3 + s];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { wsum += wq[i]; acc = fmaf(wq[i], f[i], acc); }
-        if (nl) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { nwsum += (double)wq[i]; nacc = fma((double)wq[i], (double)g[i], nacc); }
-        }
-    });
-    if (live) out[(int64_t)j * 32 + s] = acc * (wsum > 0.f ? 1.f / wsum : 0.f);
-    if (live && nl) nsum_out[(int64_t)j * 3 + s] = (float)nacc;
-    if (live && nl && s == 0) wsum_out[j] = (float)nwsum;
-}
-
 // ---- UDF mask branch (NeuralField, models/nksr_net.py:124-130) -------------------------------------------------
-// Plane features of one level: per voxel j the trilinear-weighted centroid offset (voxel units, relative
-// to the voxel centre) and mean normal of the surrounding points.  out [n, 8] = (occupied, off xyz,
-// unit normal xyz, 0).  One thread per voxel, same gather form (and point order) as k_splat_mean_c.
-__global__ void k_splat_plane(const float* __restrict__ xyz, const float* __restrict__ nrm, const int32_t* __restrict__ start,
-                              const int32_t* __restrict__ end, const int32_t* __restrict__ nbr,
-                              const int32_t* __restrict__ ijk, int n, float inv_w, float* __restrict__ out) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const float cx = (float)ijk[j * 3] + 0.5f, cy = (float)ijk[j * 3 + 1] + 0.5f, cz = (float)ijk[j * 3 + 2] + 0.5f;
-    float wsum = 0.f, ox = 0.f, oy = 0.f, oz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
-    for (int s = 0; s < 27; ++s) {
-        const int c = nbr[(int64_t)j * 27 + s];
-        if (c < 0) continue;
-        for (int k = start[c]; k < end[c]; ++k) {
-            const float rx = __fmul_rn(xyz[(int64_t)k * 3], inv_w) - cx, ry = __fmul_rn(xyz[(int64_t)k * 3 + 1], inv_w) - cy,
-                        rz = __fmul_rn(xyz[(int64_t)k * 3 + 2], inv_w) - cz;
-            const float wx = 1.f - fabsf(rx), wy = 1.f - fabsf(ry), wz = 1.f - fabsf(rz);
-            if (wx <= 0.f || wy <= 0.f || wz <= 0.f) continue;
-            const float w = wx * wy * wz;
-            wsum += w;
-            ox = fmaf(w, rx, ox); oy = fmaf(w, ry, oy); oz = fmaf(w, rz, oz);
-            nx = fmaf(w, nrm[(int64_t)k * 3], nx); ny = fmaf(w, nrm[(int64_t)k * 3 + 1], ny); nz = fmaf(w, nrm[(int64_t)k * 3 + 2], nz);
-        }
-    }
-    float* o = out + (int64_t)j * 8;
-    const float inv = wsum > 0.f ? 1.f / wsum : 0.f;
-    const float nn = sqrtf(nx * nx + ny * ny + nz * nz);
-    const float invn = nn > 1e-8f ? 1.f / nn : 0.f;
-    o[0] = wsum > 0.f ? 1.f : 0.f;
-    o[1] = ox * inv; o[2] = oy * inv; o[3] = oz * inv;
-    o[4] = nx * invn; o[5] = ny * invn; o[6] = nz * invn;
-    o[7] = 0.f;
-}
-
+// feat [n, 8]: the plane features of a level, (occupied, off xyz, unit normal xyz, 0) per voxel (splat.hip: k_splat_plane).
 // udf(x) = w_d | sum_c t_c(x) <x/w_d - centre_c - off_c, n_c> | / sum_c t_c(x) over the occupied voxels among
 // the 8 centres surrounding x (t = trilinear weight); NKSR_UDF_FAR where none is occupied.  With
 // only_unset, queries that already hold a value from a finer level are left alone.
@@ -437,14 +300,6 @@ __global__ void k_linear(const float* __restrict__ in, int64_t n, const float* _
     out[t] = a;
 }
 
-#define LAUNCH1D(kern, n, stream, ...)                                                              \
-    do {                                                                                            \
-        if ((n) > 0) {                                                                              \
-            hipLaunchKernelGGL(kern, dim3(nksr_blocks((n), 256)), dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__); \
-            NKSR_CHECK_LAUNCH();                                                                    \
-        }                                                                                           \
-    } while (0)
-
 extern "C" int nksr_point_mlp(const float* xyz, const float* feat, int64_t n, float inv_w0, int C, const float* W1,
                               const float* b1, const float* W2, const float* b2, float* out, void* stream) {
     if (C != NN_C) return nksr_set_error(NKSR_ERR_ARG, "unet.f_maps must be %d", NN_C);
@@ -452,21 +307,6 @@ extern "C" int nksr_point_mlp(const float* xyz, const float* feat, int64_t n, fl
     if (!xyz || !feat || !W1 || !b1 || !W2 || !b2 || !out) return nksr_set_error(NKSR_ERR_ARG, "point_mlp: NULL arrays");
     if ((uintptr_t)out & 15) return nksr_set_error(NKSR_ERR_ARG, "point_mlp: out must be 16-byte aligned (rows leave as 16-byte pieces)");
     LAUNCH1D(k_point_mlp, n, stream, xyz, feat, n, inv_w0, W1, b1, W2, b2, out);
-    return NKSR_OK;
-}
-extern "C" int nksr_splat_mean(const float* xyz_sorted, const float* feat_sorted, int C, const int32_t* start,
-                               const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* out,
-                               void* stream) {
-    if (C < 1 || C > 64) return nksr_set_error(NKSR_ERR_ARG, "splat_mean supports 1..64 channels");
-    if (n <= 0) return NKSR_OK;
-    if (!xyz_sorted || !feat_sorted || !start || !end || !nbr || !ijk || !out) return nksr_set_error(NKSR_ERR_ARG, "splat_mean: NULL arrays");
-    if (C == 32) {
-        hipLaunchKernelGGL(k_splat_mean32, dim3(nksr_blocks((int64_t)n * 32, 256)), dim3(256), 0, (hipStream_t)stream, xyz_sorted, feat_sorted, start, end,
-                           nbr, ijk, n, inv_w, out);
-        NKSR_CHECK_LAUNCH();
-        return NKSR_OK;
-    }
-    LAUNCH1D(k_splat_mean_c, (int64_t)n * ((C + 7) / 8), stream, xyz_sorted, feat_sorted, C, start, end, nbr, ijk, n, inv_w, out);
     return NKSR_OK;
 }
 extern "C" int nksr_sparse_conv3(const float* in, const int32_t* nbr, int32_t n, int C, const float* W, const float* bias,
@@ -486,17 +326,6 @@ extern "C" int nksr_pool_children(const float* child_feat, const int32_t* start,
     if (n_parent <= 0) return NKSR_OK;
     if (!child_feat || !start || !end || !out) return nksr_set_error(NKSR_ERR_ARG, "pool_children: NULL arrays");
     LAUNCH1D(k_pool_children, (int64_t)n_parent * C, stream, child_feat, start, end, n_parent, C, out);
-    return NKSR_OK;
-}
-extern "C" int nksr_splat_encode(const float* xyz_sorted, const float* feat_sorted, const float* normal_sorted, const int32_t* start,
-                                 const int32_t* end, const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* voxel_feat,
-                                 float* normal_sum, float* weight_sum, void* stream) {
-    if (n <= 0) return NKSR_OK;
-    if (!xyz_sorted || !feat_sorted || !start || !end || !nbr || !ijk || !voxel_feat) return nksr_set_error(NKSR_ERR_ARG, "splat_encode: NULL arrays");
-    if (normal_sorted && (!normal_sum || !weight_sum)) return nksr_set_error(NKSR_ERR_ARG, "splat_encode: NULL normal_sum / weight_sum with normals given");
-    hipLaunchKernelGGL(k_splat_encode32, dim3(nksr_blocks((int64_t)n * 32, 256)), dim3(256), 0, (hipStream_t)stream, xyz_sorted, feat_sorted,
-                       normal_sorted, start, end, nbr, ijk, n, inv_w, voxel_feat, normal_sum, weight_sum);
-    NKSR_CHECK_LAUNCH();
     return NKSR_OK;
 }
 extern "C" int nksr_gather_rows(const float* src, const int32_t* idx, int64_t n, int C, const float* add, float* out,
@@ -519,14 +348,6 @@ extern "C" int nksr_linear(const float* in, int64_t n, int Cin, const float* W, 
     if (n <= 0) return NKSR_OK;
     if (!in || !W || !out) return nksr_set_error(NKSR_ERR_ARG, "linear: NULL arrays");      // (b: optional)
     LAUNCH1D(k_linear, n * Cout, stream, in, n, W, b, Cout, out);
-    return NKSR_OK;
-}
-
-extern "C" int nksr_splat_plane(const float* xyz_sorted, const float* normal_sorted, const int32_t* start, const int32_t* end,
-                                const int32_t* nbr, const int32_t* ijk, int32_t n, float inv_w, float* out, void* stream) {
-    if (n <= 0) return NKSR_OK;
-    if (!xyz_sorted || !normal_sorted || !start || !end || !nbr || !ijk || !out) return nksr_set_error(NKSR_ERR_ARG, "splat_plane: NULL arrays");
-    LAUNCH1D(k_splat_plane, n, stream, xyz_sorted, normal_sorted, start, end, nbr, ijk, n, inv_w, out);
     return NKSR_OK;
 }
 extern "C" int nksr_udf_decode(const nksr_level_t* level, int level_index, const float* feat, const float* xyz, int64_t n,

@@ -82,7 +82,7 @@ class EncodedCloud:
         self.normal_splat = None      # (grid, depth, normal_sum, weight_sum) of the encoder's grid, where its pass formed them
 
 
-# ---- thin wrappers over csrc/nn.hip ---------------------------------------------------------------------
+# ---- thin wrappers over csrc/nn.hip, splat.hip, hierarchy.hip ---------------------------------------------------------------------
 def sort_cloud(xyz, feat, inv_w0):
     n = xyz.shape[0]
     keys = torch.empty(n, dtype=torch.int64, device=xyz.device)
@@ -100,58 +100,46 @@ def site_ranges(site_keys, grid, shift_level):
     return st, en
 
 
+def _splat(entry, grid, d, inv_w0, site_keys, xyz_sorted, point_args, widths):
+    """One splat launch (csrc/splat.hip) onto level-d ``grid``: ``point_args`` are the entry point's arguments between the sorted
+    points and the cell ranges (tensors or None: passed as pointers; channel counts); ``widths`` the row widths of its fp32 outputs
+    (0: one value per voxel, None: absent, passed as NULL).
+    The kernels carry no point count and read point 0 unconditionally: no launch on an empty cloud, zeros."""
+    n, empty = grid.num_voxels, xyz_sorted.shape[0] == 0
+    new = torch.zeros if empty else torch.empty
+    outs = [None if w is None else new((n, w) if w else n, dtype=torch.float32, device=grid.device) for w in widths]
+    if not empty:
+        st, en = site_ranges(site_keys, grid, d)
+        call(entry, ptr(xyz_sorted), *[a if isinstance(a, int) else ptr(a) for a in point_args], ptr(st), ptr(en), ptr(grid.nbr),
+             ptr(grid.ijk), n, float(inv_w0 * 2.0 ** (-d)), *[ptr(o) for o in outs], stream())
+    return outs
+
+
 def splat_trilinear(grid, d, inv_w0, site_keys, xyz_sorted, feat_sorted):
     """Weighted SUM (and weight sum) of <= 8-channel features splatted onto level-d ``grid``."""
-    n, C_ = grid.num_voxels, feat_sorted.shape[1]
-    if xyz_sorted.shape[0] == 0:      # the kernels carry no point count and read point 0 unconditionally: no launch on an empty cloud
-        return torch.zeros((n, C_), dtype=torch.float32, device=grid.device), torch.zeros(n, dtype=torch.float32, device=grid.device)
-    st, en = site_ranges(site_keys, grid, d)
-    out = torch.empty((n, C_), dtype=torch.float32, device=grid.device)
-    ws = torch.empty(n, dtype=torch.float32, device=grid.device)
-    call('nksr_splat_trilinear', ptr(xyz_sorted), ptr(feat_sorted), C_, ptr(st), ptr(en), ptr(grid.nbr), ptr(grid.ijk), n,
-         float(inv_w0 * 2.0 ** (-d)), ptr(out), ptr(ws), stream())
+    C_ = feat_sorted.shape[1]
+    out, ws = _splat('nksr_splat_trilinear', grid, d, inv_w0, site_keys, xyz_sorted, (feat_sorted, C_), (C_, 0))
     return out, ws
 
 
 def splat_mean(grid, d, inv_w0, site_keys, xyz_sorted, feat_sorted):
-    n, C_ = grid.num_voxels, feat_sorted.shape[1]
-    if xyz_sorted.shape[0] == 0:      # (as splat_trilinear)
-        return torch.zeros((n, C_), dtype=torch.float32, device=grid.device)
-    st, en = site_ranges(site_keys, grid, d)
-    out = torch.empty((n, C_), dtype=torch.float32, device=grid.device)
-    call('nksr_splat_mean', ptr(xyz_sorted), ptr(feat_sorted), C_, ptr(st), ptr(en), ptr(grid.nbr), ptr(grid.ijk), n,
-         float(inv_w0 * 2.0 ** (-d)), ptr(out), stream())
-    return out
+    C_ = feat_sorted.shape[1]
+    return _splat('nksr_splat_mean', grid, d, inv_w0, site_keys, xyz_sorted, (feat_sorted, C_), (C_,))[0]
 
 
 def splat_encode(grid, d, inv_w0, site_keys, xyz_sorted, feat_sorted, normal_sorted=None):
     """One pass over the points for both splats of the encoder: ``splat_mean`` of the 32-channel ``feat_sorted`` and -- with
     ``normal_sorted`` [N, 3] -- ``splat_trilinear`` of it on the same grid: (voxel_feat, normal_sum or None, weight_sum or None)."""
-    n, dev = grid.num_voxels, grid.device
-    new = torch.zeros if xyz_sorted.shape[0] == 0 else torch.empty      # (as splat_trilinear: no launch on an empty cloud, zeros)
-    out = new((n, feat_sorted.shape[1]), dtype=torch.float32, device=dev)
-    ns = new((n, 3), dtype=torch.float32, device=dev) if normal_sorted is not None else None
-    ws = new(n, dtype=torch.float32, device=dev) if normal_sorted is not None else None
-    if xyz_sorted.shape[0] == 0:
-        return out, ns, ws
-    if feat_sorted.shape[1] != 32 or (normal_sorted is not None and normal_sorted.shape[1] != 3):
+    if xyz_sorted.shape[0] and (feat_sorted.shape[1] != 32 or (normal_sorted is not None and normal_sorted.shape[1] != 3)):
         raise RuntimeError('splat_encode takes 32 feature channels and 3 normal channels')
-    st, en = site_ranges(site_keys, grid, d)
-    call('nksr_splat_encode', ptr(xyz_sorted), ptr(feat_sorted), ptr(normal_sorted), ptr(st), ptr(en), ptr(grid.nbr), ptr(grid.ijk), n,
-         float(inv_w0 * 2.0 ** (-d)), ptr(out), ptr(ns), ptr(ws), stream())
+    widths = (feat_sorted.shape[1], 3, 0) if normal_sorted is not None else (feat_sorted.shape[1], None, None)
+    out, ns, ws = _splat('nksr_splat_encode', grid, d, inv_w0, site_keys, xyz_sorted, (feat_sorted, normal_sorted), widths)
     return out, ns, ws
 
 
 def splat_plane(grid, d, inv_w0, site_keys, xyz_sorted, normal_sorted):
-    """Plane features [n, 8] = (occupied, centroid offset, unit mean normal, 0) of level-d ``grid``."""
-    n = grid.num_voxels
-    if xyz_sorted.shape[0] == 0:      # (as splat_trilinear): no voxel is occupied
-        return torch.zeros((n, 8), dtype=torch.float32, device=grid.device)
-    st, en = site_ranges(site_keys, grid, d)
-    out = torch.empty((n, 8), dtype=torch.float32, device=grid.device)
-    call('nksr_splat_plane', ptr(xyz_sorted), ptr(normal_sorted), ptr(st), ptr(en), ptr(grid.nbr), ptr(grid.ijk), n,
-         float(inv_w0 * 2.0 ** (-d)), ptr(out), stream())
-    return out
+    """Plane features [n, 8] = (occupied, centroid offset, unit mean normal, 0) of level-d ``grid`` (empty cloud: none occupied)."""
+    return _splat('nksr_splat_plane', grid, d, inv_w0, site_keys, xyz_sorted, (normal_sorted,), (8,))[0]
 
 
 def gather_rows(src, idx, add=None):

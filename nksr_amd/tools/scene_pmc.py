@@ -25,7 +25,7 @@ GROUPS = [
 if os.environ.get('NKSR_PMC_GROUPS'):       # e.g. "0,1,7": a quick look at the issue / wait split only
     GROUPS = [GROUPS[int(i)] for i in os.environ['NKSR_PMC_GROUPS'].split(',')]
 LAST_BENCH_LINE = None
-KERNELS = ['k_cell_blocks', 'k_fz_cells', 'k_cheb16_step', 'k_kernel_rows', 'k_sparse_conv3', 'k_splat_mean32', 'k_splat_encode32', 'k_splat_trilinear',
+KERNELS = ['k_cell_blocks', 'k_fz_cells', 'k_cheb16_step', 'k_kernel_rows', 'k_sparse_conv3', 'k_splat_encode32', 'k_splat_trilinear',
            'k_fz_gather', 'k_fz_cellsum', 'k_evaluate_f', 'k_build_nbr', 'k_row_count', 'k_row_fill']
 
 

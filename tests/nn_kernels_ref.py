@@ -1,4 +1,4 @@
-"""numpy references, inputs and check functions for the sparse-network kernels (csrc/nn.hip, k_splat_trilinear of csrc/hierarchy.hip,
+"""numpy references, inputs and check functions for the sparse-network kernels (csrc/nn.hip, the splats of csrc/splat.hip with
 splat_for_each_point of csrc/common.h), one kernel at a time.  tests/test_nn_kernels_ref_cpu.py verifies them without a GPU (against
 oracle/network.py, against fp32 evaluations in another order, and against deliberately wrong evaluations); tests/test_gpu_nn_kernels.py
 hands the kernels' outputs to the same check functions.

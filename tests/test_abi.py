@@ -229,7 +229,7 @@ def test_c_abi_argument_errors_without_a_gpu():
                                     C.c_int(4), C.c_float(0.02), C.c_int(0), one, null, one, null) != 0 and 'nb_points' in err()
     assert lib.nksr_sdf_from_points(one, one, null, null, null, null, null, C.c_int32(0), C.c_float(1.0), C.c_float(1.0), one, C.c_int64(1), C.c_int(8),
                                     C.c_int(4), C.c_float(0.0), C.c_int(0), one, null, one, null) != 0 and 'stdv' in err()
-    # the network kernels (csrc/nn.hip, nksr_splat_trilinear): with n > 0 a NULL array, a channel count the kernel is not built for
+    # the network kernels (csrc/nn.hip, csrc/splat.hip): with n > 0 a NULL array, a channel count the kernel is not built for
     # or a misaligned in / W / out is an argument error before any launch; n <= 0 is a no-op
     big = (C.c_float * 4096)()
     a16 = (C.addressof(big) + 15) & ~15            # a 16-byte aligned host address (never dereferenced: every call below fails first)

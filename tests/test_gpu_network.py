@@ -1,4 +1,4 @@
-"""GPU parity of the sparse feature-hierarchy network (csrc/nn.hip: point MLP, splat-mean, fp32-MFMA
+"""GPU parity of the sparse feature-hierarchy network (csrc/nn.hip and csrc/splat.hip: point MLP, splat-mean, fp32-MFMA
 sparse convolution, child pooling, transfer/up-sampling, heads, top-down structure pruning) against
 oracle/network.py with the same exported parameters."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Every sparse-network kernel alone (csrc/nn.hip, k_splat_trilinear of csrc/hierarchy.hip, splat_for_each_point of csrc/common.h)
+"""Every sparse-network kernel alone (csrc/nn.hip, the splats of csrc/splat.hip with splat_for_each_point of csrc/common.h)
 against the exact and fp64 references of tests/nn_kernels_ref.py, which tests/test_nn_kernels_ref_cpu.py verifies without a GPU.
 
 Family A inputs sit on a lattice where every fp32 sum is exact: those comparisons are bit for bit (2 ulp behind a division or a square

@@ -1,4 +1,4 @@
-"""The encoder's one pass over the points (csrc/nn.hip: k_splat_encode32) against the two kernels it stands for, and
+"""The encoder's one pass over the points (csrc/splat.hip: k_splat_encode32) against the two kernels it stands for, and
 the U-Net's normal target taken from it by index against the splat on the candidate grid that it replaces.  Every comparison is bit
 for bit (torch.equal on int32 views: +0.0 and -0.0 differ).
 
