@@ -41,7 +41,8 @@ def check(name, measured, bound):
 
 def field_inputs(xyz, dev, K=4, H=16, depth=4, init_scale=0.5, seed=0, random_feats=True):
     """The same hierarchy (cells of the points ``xyz`` and their 26 neighbours), features and interpolators on both sides:
-    (oracle hierarchy, SparseFeatureHierarchy, features per level, oracle interpolators, network)."""
+    (oracle hierarchy, SparseFeatureHierarchy, features per level, oracle interpolators, network).  ``dev`` None: the oracle side
+    alone (no GPU), the SparseFeatureHierarchy is None."""
     import torch
     import nksr_amd
     from nksr_amd import configs
@@ -56,7 +57,7 @@ def field_inputs(xyz, dev, K=4, H=16, depth=4, init_scale=0.5, seed=0, random_fe
         it.b2.data = torch.from_numpy(rs.randn(H).astype(np.float32) * 0.2)
         it.b3.data = torch.from_numpy(rs.randn(K).astype(np.float32) * 0.05)
     oh = hierarchy.Hierarchy(0.1, depth).build_point_neighborhood(xyz)
-    svh = nksr_amd.SparseFeatureHierarchy(0.1, depth, dev).build_point_neighborhood(torch.from_numpy(xyz).to(dev))
+    svh = nksr_amd.SparseFeatureHierarchy(0.1, depth, dev).build_point_neighborhood(torch.from_numpy(xyz).to(dev)) if dev is not None else None
     feats = []
     for L in oh.levels:
         f = np.zeros((L.n, K), np.float32)
