@@ -677,6 +677,53 @@ int nksr_plane_score(const float* xyz, int64_t n, const double* planes, int64_t 
 int nksr_plane_moments(const float* xyz, int64_t n, const double* plane, const double* centre, double threshold, uint8_t* mask_out,
                        double* partials_out, void* stream);
 
+/* ---- global registration (csrc/fpfh.hip, csrc/global_register.hip; nksr_amd/global_register.py: cloud.compute_fpfh_feature,
+ * cloud.match_features, cloud.registration_ransac_based_on_feature_matching) ------------------------------------------------------
+ * Fast Point Feature Histograms.  xyz / normal [n, 3] fp32 in ONE order (normals of unit length), idx [n, k] (int32, indices into that
+ * order) and d2 [n, k] (fp32) = the k neighbours of every point and their squared distances, 1 <= k <= NKSR_FPFH_MAX_K.  Neighbour m
+ * of point i, j = idx[i, m], TAKES PART iff d2[i, m] <= fl32(radius)^2 (the fp32 product), d2[i, m] > 0 and the cross product v below
+ * is not (0, 0, 0).  Pair features: fp64 from the fp32 inputs widened, every product and sum rounded on its own (no fused
+ * multiply-add), a dot product a.b = (a_x b_x + a_y b_y) + a_z b_z, a cross product (a x b)_x = a_y b_z - a_z b_y (cyclic):
+ *   d = x_j - x_i, L = sqrt(d.d), a1 = (n_i.d) / L, a2 = (n_j.d) / L
+ *   |a1| < |a2|:  u = n_j, o = n_i, d <- -d, f2 = -a2;     otherwise:  u = n_i, o = n_j, f2 = a1
+ *   v = d x u, |v| = sqrt(v.v), v <- v / |v| per component;  w = u x v;  f1 = v.o;  f0 = atan2(w.o, u.o)
+ *   b0 = floor((11 (f0 + pi)) / (2 pi)), b1 = floor((11 (f1 + 1)) / 2), b2 = floor((11 (f2 + 1)) / 2), each clamped to 0 .. 10
+ * nksr_spfh: count_out [n, NKSR_FPFH_BINS] (int32) = per point the number of its participating neighbours in bins b0, 11 + b1 and
+ *   22 + b2; n_out [n] (int32) = their number; mask_out [n] (uint32) = bit m set iff neighbour m takes part.  Integers only, no
+ *   atomics.  n == 0: nothing is touched.
+ * nksr_fpfh: out [n, NKSR_FPFH_BINS] (fp32) from count / n_nb / mask as nksr_spfh wrote them, all fp64 in this order:
+ *   S[i, b] = (double) count[i, b] * (100 / (double) n_nb[i]), 0 where n_nb[i] = 0;
+ *   F[i, b] = sum over the set bits m of mask[i], ascending, one after another: S[idx[i, m], b] / (double) d2[i, m];
+ *   per third g = 0, 1, 2: s_g = the sum of F[i, 11 g .. 11 g + 10] in ascending b; s_g > 0: F[i, b] <- F[i, b] * (100 / s_g);
+ *   out[i, b] = fl32(F[i, b] + S[i, b]).  Fixed order, no atomics: the same call gives the same bits.
+ * nksr_feature_match: for every row a of A [na, NKSR_FPFH_BINS] (fp32) the row b of B [nb, NKSR_FPFH_BINS] with the smallest
+ *   D = sum_j (A[a, j] - B[b, j])^2, accumulated in fp32 in ascending j (difference, product, sum, each rounded on its own; no
+ *   expansion of the square), the lowest b among equal D.  idx_out [na] (int32) = b, dist2_out [na] = D; a row of A for which no b
+ *   gives a finite D (a NaN or an infinity in it, or nb == 0) has idx -1 and dist2 +inf.  keys_work [na] (uint64) is scratch: the
+ *   rows of B are split over workgroups whose partial answers meet in one integer atomicMin on (bits of D) << 32 | b -- D >= 0, so
+ *   its bits order as an integer; no floating-point atomics.  na == 0: nothing is touched.  na, nb < 2^31.
+ * nksr_pose_score: pairs (p, q) = (src [n_pairs, 3], tgt [n_pairs, 3]) fp32; transforms [n_hyp, 12] (fp64, device) = the upper three
+ *   rows of 4 x 4 matrices, row-major.  p' = R p + t as nksr_icp_accumulate states it, e = p' - q, inlier iff
+ *   (e_x e_x + e_y e_y) + e_z e_z <= threshold * threshold (fp64, no fused multiply-add).  counts_out [n_hyp] (int32) = the inliers
+ *   of every transform, -1 for one with an entry that is not finite.  Integer atomics only.  n_hyp <= NKSR_POSE_MAX_H.
+ * nksr_corr_accumulate: the rows of nksr_icp_accumulate's method 0 (NKSR_ICP_COUNT, NKSR_ICP_D2, NKSR_ICP_PT_P, _Q, _PQ; zeros
+ *   behind) over the inliers -- the test above -- of ONE transform [12] among given pairs, about centre [3] (both device):
+ *   partials_out [ceil(n_pairs / NKSR_ICP_BLOCK), NKSR_ICP_FIELDS], the same fixed order (the rows go to nksr_icp_reduce);
+ *   mask_out [n_pairs] (uint8) = inlier.  n_pairs == 0: nothing is touched. */
+#define NKSR_FPFH_BINS 33
+#define NKSR_FPFH_MAX_K 32
+#define NKSR_POSE_MAX_H (1 << 20)
+int nksr_spfh(const float* xyz, const float* normal, int64_t n, const int32_t* idx, const float* d2, int k, float radius,
+              int32_t* count_out, int32_t* n_out, uint32_t* mask_out, void* stream);
+int nksr_fpfh(const int32_t* count, const int32_t* n_nb, const uint32_t* mask, int64_t n, const int32_t* idx, const float* d2, int k,
+              float* out, void* stream);
+int nksr_feature_match(const float* A, int64_t na, const float* B, int64_t nb, uint64_t* keys_work, int32_t* idx_out, float* dist2_out,
+                       void* stream);
+int nksr_pose_score(const float* src, const float* tgt, int64_t n_pairs, const double* transforms, int64_t n_hyp, double threshold,
+                    int32_t* counts_out, void* stream);
+int nksr_corr_accumulate(const float* src, const float* tgt, int64_t n_pairs, const double* transform, const double* centre,
+                         double threshold, uint8_t* mask_out, double* partials_out, void* stream);
+
 /* ---- voxel reduction of a point cloud (csrc/cloud.hip; nksr_amd/cloud.py voxel_downsample) -----------------------------------
  * order [n] = point indices sorted by voxel key, start / end [n_vox] = the run of every voxel in it (nksr_run_table_u64 of the sorted
  * keys: start_out without its last entry, and without its first). mean_xyz_out [n_vox, 3] and mean_attr_out [n_vox, C] = the mean of xyz [n, 3] and of attr [n, C] (C = 0: attr and

@@ -4,8 +4,9 @@ Exports the surface of the reference's ``nksr`` package that its examples and tr
 use: ``Reconstructor``, ``NKSRNetwork``, ``SparseFeatureHierarchy``,
 ``get_estimate_normal_preprocess_fn`` and the sub-modules ``fields``, ``svh``, ``configs``,
 ``utils``; beyond it the mesh and point-cloud tools (``metrics``, ``MeshTopology``, ``MeshGeometry``, ``MeshSimplifier``, ``MeshSlicer``, ``MeshBoundary``, ``cloud`` -- neighbour queries, voxel downsampling, outlier masks, normal
-orientation, rigid registration (``cloud.icp`` / ``icp_multiscale`` / ``evaluate_registration`` / ``apply_transform``) and
-segmentation (``cloud.cluster_dbscan`` / ``segment_plane``) -- and the
+orientation, rigid registration (``cloud.icp`` / ``icp_multiscale`` / ``evaluate_registration`` / ``apply_transform``), global
+registration of scans that share no frame (``cloud.compute_fpfh_feature`` / ``match_features`` /
+``registration_ransac_based_on_feature_matching`` / ``register_global``) and segmentation (``cloud.cluster_dbscan`` / ``segment_plane``) -- and the
 ``preprocess_fn`` makers on it).  ``import nksr`` resolves to this package through the top-level ``nksr`` shim.
 """
 from . import cloud, configs, fields, metrics, svh, utils

@@ -15,6 +15,9 @@ the neighbour search the package already runs for its normals, its SDF ground tr
     csrc/register.hip): rigid registration of one cloud onto another, point-to-point or point-to-plane, before scans are merged.
   * ``cluster_dbscan`` / ``segment_plane`` / ``plane_scores`` / ``sample_planes`` / ``DbscanResult`` (nksr_amd/segment.py,
     csrc/segment.hip): a scene split into its objects -- density-based clusters, and the dominant plane found by RANSAC.
+  * ``compute_fpfh_feature`` / ``match_features`` / ``registration_ransac_based_on_feature_matching`` / ``register_global`` /
+    ``FpfhFeature`` / ``RansacResult`` (nksr_amd/global_register.py, csrc/fpfh.hip, csrc/global_register.hip): a pose for scans
+    that share no frame -- FPFH features, matched by brute force, RANSAC over the matched pairs -- handed to ``icp``.
 ``nksr_amd.preprocess`` wraps them as ``preprocess_fn`` for ``Reconstructor.reconstruct``.  GPU tensors only.
 """
 import torch
@@ -25,6 +28,8 @@ from .neighbours import MAX_K, _RINGS, PointGrid, PointPyramid, _grid_args, choo
 from .orient import OrientedNormals, estimate_normals, orient_graph, orient_normals  # noqa: F401  (part of this module's surface)
 from .register import IcpResult, apply_transform, evaluate_registration, icp, icp_multiscale  # noqa: F401  (part of this module's surface)
 from .segment import DbscanResult, cluster_dbscan, plane_scores, sample_planes, segment_plane  # noqa: F401  (part of this module's surface)
+from .global_register import (FpfhFeature, RansacResult, compute_fpfh_feature, match_features, register_global,  # noqa: F401  (part of this module's surface)
+                              registration_ransac_based_on_feature_matching)
 from .svh import inv_w0_f32
 
 
@@ -89,6 +94,11 @@ class CloudIndex:
     def knn(self, k, query=None, exclude_self=False):
         """-> (idx int64 [Q, k], dist float32 [Q, k] ascending).  ``query=None``: the cloud itself, row i = point i.  ``exclude_self``
         (self-queries only): point i is left out of its own row; other points at the same position are not."""
+        idx, d2 = self.knn_d2(k, query, exclude_self)
+        return idx, torch.sqrt(d2)
+
+    def knn_d2(self, k, query=None, exclude_self=False):
+        """``knn`` with the SQUARED fp32 distances as the kernel wrote them (what the feature kernels are defined on)."""
         k = int(k)
         ex = bool(exclude_self)
         if k < 1 or k > MAX_K:
@@ -131,7 +141,7 @@ class CloudIndex:
             return good
 
         search_every_scale(self.xyz, self.pyramid, run, k, nq, None, 'knn: %%d queries found no %d neighbours' % k)
-        return out_idx, torch.sqrt(out_d2)
+        return out_idx, out_d2
 
     def mean_knn_distance(self, k):
         """float32 [N]: mean distance of every point to its k nearest OTHER points (the mean is taken in fp64 and rounded once)."""
@@ -194,6 +204,11 @@ class CloudIndex:
             lo, hi, _ = bbox_center(self.xyz)
             self._centre = 0.5 * (lo.double() + hi.double()).cpu().numpy()
         return self._centre
+
+    def compute_fpfh_feature(self, normal, radius, max_nn=32):
+        """``global_register.compute_fpfh_feature`` on this index: ``normal`` [N, 3] -> ``FpfhFeature`` (rows in the caller's order)."""
+        from .global_register import fpfh_on_index
+        return fpfh_on_index(self, normal, radius, max_nn)
 
     def icp(self, source, max_correspondence_distance, **kwargs):
         """``register.icp`` with this cloud as the target: one index serves many sources.  -> ``IcpResult``."""

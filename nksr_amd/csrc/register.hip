@@ -14,6 +14,7 @@
 // an index and twelve coordinates.  The terms are formed without fused multiply-adds, in the order include/nksr_hip.h states: a host
 // restatement in plain fp64 arithmetic gets every term to the last bit, and differs from the sums by the summation order alone.
 #include "common.h"
+#include "icp_dev.h"
 #include "knn_dev.h"
 #include "wave_dev.h"
 
@@ -21,52 +22,6 @@
 static_assert(NKSR_ICP_BLOCK % NKSR_WAVE == 0 && NKSR_ICP_FIELDS <= NKSR_ICP_BLOCK, "whole wavefronts, one lane per field at the end");
 static_assert(NKSR_ICP_PT_PQ + 9 <= NKSR_ICP_FIELDS && NKSR_ICP_PL_JJ + 21 == NKSR_ICP_PL_JR && NKSR_ICP_PL_JR + 6 == NKSR_ICP_PL_RR &&
               NKSR_ICP_PL_RR < NKSR_ICP_FIELDS, "layout of the sums");
-
-// p = R s + t, every product and sum rounded on its own
-__device__ __forceinline__ void icp_transform(const double* __restrict__ T, const float s[3], double p[3]) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double u = T[4 * a] * (double)s[0] + T[4 * a + 1] * (double)s[1];
-        const double v = u + T[4 * a + 2] * (double)s[2];
-        p[a] = v + T[4 * a + 3];
-    }
-}
-
-// the terms of one correspondence (p, q) -- and of its normal n for the plane method -- about the centre c
-template <int METHOD>
-__device__ __forceinline__ void icp_terms(const double p[3], const double q[3], const float* __restrict__ nrm, const double c[3],
-                                          double term[NKSR_ICP_FIELDS]) {
-#pragma clang fp contract(off)
-    const double d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
-    const double pp[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
-    term[NKSR_ICP_COUNT] = 1.0;
-    const double dxy = d[0] * d[0] + d[1] * d[1];
-    term[NKSR_ICP_D2] = dxy + d[2] * d[2];
-    if (METHOD == 0) {
-        const double qq[3] = {q[0] - c[0], q[1] - c[1], q[2] - c[2]};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            term[NKSR_ICP_PT_P + a] = pp[a];
-            term[NKSR_ICP_PT_Q + a] = qq[a];
-#pragma unroll
-            for (int b = 0; b < 3; ++b) term[NKSR_ICP_PT_PQ + 3 * a + b] = pp[a] * qq[b];
-        }
-    } else {
-        const double n[3] = {(double)nrm[0], (double)nrm[1], (double)nrm[2]};
-        const double rxy = n[0] * d[0] + n[1] * d[1];
-        const double r = rxy + n[2] * d[2];
-        const double J[6] = {pp[1] * n[2] - pp[2] * n[1], pp[2] * n[0] - pp[0] * n[2], pp[0] * n[1] - pp[1] * n[0], n[0], n[1], n[2]};
-        int k = NKSR_ICP_PL_JJ;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-#pragma unroll
-            for (int b = a; b < 6; ++b) term[k++] = J[a] * J[b];
-            term[NKSR_ICP_PL_JR + a] = J[a] * r;
-        }
-        term[NKSR_ICP_PL_RR] = r * r;
-    }
-}
 
 template <int METHOD>
 __global__ void __launch_bounds__(NKSR_ICP_BLOCK) k_icp_accumulate(KnnGrid g, const int64_t* __restrict__ perm, const float* __restrict__ nrm,
