@@ -1259,6 +1259,21 @@ int nksr_orient_apply(const float* xyz, const float* normal, int64_t n, const in
                       const int32_t* min_index, int mode, float vx, float vy, float vz, uint8_t* flipped_out, float* normal_out,
                       int32_t* parent_out, int32_t* root_flags_out, void* stream);
 
+/* ---- moving-least-squares projection (csrc/mls.hip; nksr_amd/mls.py: cloud.mls_project, cloud.smooth_mls) ----------------------------
+ * Every query q is projected onto a polynomial fitted to its neighbours with Gaussian weights; csrc/mls.hip states the definition in
+ * full.  The grid as nksr_radius_count takes it (cell >= radius); neighbours: knn_d2(p - q) <= fl32(radius)^2, the predicate and the
+ * count of nksr_radius_count; weights exp(-|p - q|^2 / sigma^2) in fp64.  normal_sorted [n_ref, 3] (fp32, the grid's order) or NULL: signs
+ * the fitted normal.  query [nq, 3] or NULL: the first nq points of the sorted cloud.  order 1: the weighted least-squares plane; 2: a
+ * quadric over that plane.  min_neighbors >= 3 (order 1) / 6 (order 2).  Outputs, per query: position_out [nq, 3], normal_out [nq, 3],
+ * mean_curvature_out / gaussian_curvature_out / variation_out [nq] (fp64; NaN where they are not defined), count_out [nq] (int32: the
+ * neighbours), order_used_out [nq] (int8): 0 = not enough neighbours or collinear ones, the point is returned as it is; 1 = the plane;
+ * 2 = the quadric.  fp64 sums in a fixed order, no atomics. */
+int nksr_mls_project(const float* xyz_sorted, int64_t n_ref, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                     const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* normal_sorted, const float* query,
+                     int64_t nq, float radius, double sigma, int order, int min_neighbors, double* position_out, double* normal_out,
+                     double* mean_curvature_out, double* gaussian_curvature_out, double* variation_out, int32_t* count_out,
+                     int8_t* order_used_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

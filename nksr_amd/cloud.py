@@ -18,6 +18,8 @@ the neighbour search the package already runs for its normals, its SDF ground tr
   * ``compute_fpfh_feature`` / ``match_features`` / ``registration_ransac_based_on_feature_matching`` / ``register_global`` /
     ``FpfhFeature`` / ``RansacResult`` (nksr_amd/global_register.py, csrc/fpfh.hip, csrc/global_register.hip): a pose for scans
     that share no frame -- FPFH features, matched by brute force, RANSAC over the matched pairs -- handed to ``icp``.
+  * ``mls_project`` / ``smooth_mls`` / ``MlsResult`` (nksr_amd/mls.py, csrc/mls.hip): moving-least-squares projection -- the points
+    moved onto a polynomial fitted to their neighbours (denoising, resampling), with the fit's normals, curvatures and variation.
 ``nksr_amd.preprocess`` wraps them as ``preprocess_fn`` for ``Reconstructor.reconstruct``.  GPU tensors only.
 """
 import torch
@@ -30,6 +32,7 @@ from .register import IcpResult, apply_transform, evaluate_registration, icp, ic
 from .segment import DbscanResult, cluster_dbscan, plane_scores, sample_planes, segment_plane  # noqa: F401  (part of this module's surface)
 from .global_register import (FpfhFeature, RansacResult, compute_fpfh_feature, match_features, register_global,  # noqa: F401  (part of this module's surface)
                               registration_ransac_based_on_feature_matching)
+from .mls import MlsResult, mls_project, smooth_mls  # noqa: F401  (part of this module's surface)
 from .svh import inv_w0_f32
 
 
@@ -195,6 +198,13 @@ class CloudIndex:
         """``segment.cluster_dbscan`` on this index (the grid of ``radius_count(eps)``) -> ``DbscanResult``."""
         from .segment import dbscan_on_index
         return dbscan_on_index(self, eps, min_points)
+
+    # ---- moving least squares ------------------------------------------------------------------------------------------------
+    def mls_project(self, radius, normal=None, query=None, order=2, sigma=None, min_neighbors=None):
+        """``mls.mls_project`` on this index (the grid of ``radius_count(radius)``): ``query`` [Q, 3] (default: the cloud itself)
+        projected onto the fitted surface -> ``MlsResult`` (rows in the caller's order)."""
+        from .mls import mls_on_index
+        return mls_on_index(self, radius, normal, query, order, sigma, min_neighbors)
 
     # ---- registration ----------------------------------------------------------------------------------------------------------
     def bbox_centre(self):

@@ -11,37 +11,13 @@
 //      k_knn_pca_wave     the same, one wavefront per query over an LDS candidate list (the default of nksr_knn_pca_normals)
 // Queries run in Morton order where they are the cloud itself: neighbouring lanes scan the same cells.
 #include "common.h"
+#include "eig3_dev.h"
 #include "knn_walk_dev.h"
 
-// smallest eigenvector of a symmetric 3x3 matrix (cyclic Jacobi, fp64)
+// smallest eigenvector of a symmetric 3x3 matrix (cyclic Jacobi, fp64: eig3_dev.h)
 __device__ void smallest_eigvec(double a[3][3], float nrm[3]) {
-    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]);
-        if (off < 1e-30) break;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                if (fabs(a[p][q]) < 1e-300) continue;
-                const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-                for (int k = 0; k < 3; ++k) {
-                    const double akp = a[k][p], akq = a[k][q];
-                    a[k][p] = cs * akp - sn * akq;
-                    a[k][q] = sn * akp + cs * akq;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double apk = a[p][k], aqk = a[q][k];
-                    a[p][k] = cs * apk - sn * aqk;
-                    a[q][k] = sn * apk + cs * aqk;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = cs * vkp - sn * vkq;
-                    v[k][q] = sn * vkp + cs * vkq;
-                }
-            }
-    }
+    double v[3][3];
+    jacobi_eig3(a, v);
     int m = 0;
     if (a[1][1] < a[m][m]) m = 1;
     if (a[2][2] < a[m][m]) m = 2;

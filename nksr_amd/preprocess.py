@@ -5,8 +5,8 @@
 examples/recons_waymo.py:36, gis_app.py:41; CPU recipe examples/recons_waymo_cpu.py:21-41):
 kNN-PCA normals, flipped towards the sensor, grazing (> deg) points dropped.
 
-The cleaning steps in front of it (nksr_amd/cloud.py): voxel downsampling, the two outlier filters, plane removal and DBSCAN
-cluster selection, chained with ``compose_preprocess_fns``.  The filters keep the input order of the points they keep; the
+The cleaning steps in front of it (nksr_amd/cloud.py): voxel downsampling, the two outlier filters, plane removal, DBSCAN
+cluster selection and moving-least-squares smoothing, chained with ``compose_preprocess_fns``.  The filters keep the input order of the points they keep; the
 downsampler returns its voxels in ascending key order."""
 
 
@@ -83,6 +83,25 @@ def get_remove_plane_preprocess_fn(distance_threshold, num_iterations=1000, seed
         keep = torch.ones(xyz.shape[0], dtype=torch.bool, device=xyz.device)
         keep[inliers] = False
         return _select(keep, xyz, normal, sensor)
+    return fn
+
+
+def get_mls_smooth_preprocess_fn(radius, order=2, iterations=1, sigma=None):
+    """Moves every point onto the moving-least-squares surface of the cloud (``cloud.smooth_mls``: ``iterations`` projections, a plane
+    (``order=1``) or a quadric (``order=2``) fitted to the neighbours within ``radius``); normals that came in are replaced by the
+    fit's, signed by them; the sensor passes through; the order and the number of points are kept.  A point with too few neighbours
+    stays as it is.  The fit is a property of the WHOLE cloud: under ``reconstruct(..., chunk_size > 0)`` this function would run per
+    chunk, where the points near a chunk face lose the neighbours beyond it and are pulled towards the inside -- call
+    ``cloud.smooth_mls`` on the whole cloud first and pass what it returns."""
+    from .mls import _check_args
+    _check_args('get_mls_smooth_preprocess_fn', radius, order, sigma, None)
+    if isinstance(iterations, bool) or int(iterations) != iterations or int(iterations) < 1:
+        raise ValueError('get_mls_smooth_preprocess_fn: iterations must be an integer >= 1 (got %r)' % (iterations,))
+
+    def fn(xyz, normal, sensor):
+        from .cloud import smooth_mls
+        moved, fitted = smooth_mls(xyz, radius, normal=normal, iterations=iterations, order=order, sigma=sigma)
+        return moved, fitted if normal is not None else None, sensor
     return fn
 
 
