@@ -1153,6 +1153,40 @@ int nksr_slice_polylines(const int32_t* segments, const int32_t* rank, const uin
                          const int32_t* point_offset, int64_t n_polylines, const double* points, int64_t n_points, const double* normal,
                          int32_t* polyline_points_out, uint64_t* term_key_out, double* length_term_out, double* area_term_out, void* stream);
 
+/* ---- mesh clipping (nksr_amd/mesh_clip.py: MeshClipper; csrc/meshclip.hip) --------------------------------
+ * A mesh split along one family of parallel planes into ONE conforming mesh: the vertices are the input's followed by the points of
+ * the cross-sections section as they are (point p has id nv + p), and every valid face that crosses k planes becomes 2 k + 1
+ * triangles; the definition is DESIGN.md section 3.17, restated in numpy by tests/mesh_clip_ref.py.  The slab of a vertex is the
+ * number of offsets <= its height, in [0, P]; part s lies between planes s - 1 and s.  No atomics: every id is an exclusive scan plus
+ * a closed form, every write has one writer.  Sequence: nksr_slice_heights, nksr_slice_counts, nksr_exclusive_sum_i64 of both count
+ * arrays and of face_valid (seg_start, point_start, valid_start; read N, F2 and the pieces), nksr_slice_points, nksr_clip_faces,
+ * nksr_clip_attr; to explode a labelled mesh: nksr_clip_corner_keys, a stable nksr_sort_pairs_u64_u32 of the keys, nksr_run_table_u64
+ * (one new vertex per run), a stable sort of the faces by label, nksr_clip_group_faces. */
+/* Face f with corners (c0, c1, c2) of slabs (s0, s1, s2) is walked c0 -> c1 -> c2 -> c0; on a half-edge a -> b the points follow in
+ * travel order (planes s_a .. s_b - 1 ascending, or s_a - 1 .. s_b descending), a corner belongs to the piece of its slab, a point
+ * of plane j to pieces j and j + 1.  Piece s (min s .. max s) is the walk's members of s in walk order (3 to 5 of them) and is fanned
+ * from its first member: (m_0, m_i, m_i+1).  Triangle ids: face_start[f] (face_start [nf + 1] = the exclusive scan of 2 k + 1 over
+ * the valid faces, 0 for an invalid one; k = face_count of nksr_slice_counts) + the triangles of the earlier pieces + the position in
+ * the fan.  faces_out [F2, 3], face_source_out [F2] = f, face_part_out [F2] = s.  The id of the point of plane j on half-edge i is
+ * nv + point_start[halfedge_edge[3 f + i]] + (j - min(s_a, s_b)), the min being edge_lo of that edge.  by_piece = 0: one lane per
+ * face, looping over its pieces; != 0: one lane per (face, piece), which finds its face by a binary search of piece_start [nf + 1] =
+ * the exclusive scan of k + 1 over the valid faces (n_pieces its last entry) -- the same outputs.  nv + n_points and F2 < 2^31. */
+int nksr_clip_faces(const double* height, int64_t nv, const void* faces, int faces_int64, int64_t nf, const uint8_t* face_valid,
+                    const int32_t* halfedge_edge, const int64_t* point_start, int64_t n_points, const double* offsets, int64_t n_planes,
+                    const int64_t* face_start, const int64_t* piece_start, int64_t n_pieces, int64_t n_faces_out, int by_piece,
+                    int32_t* faces_out, int32_t* face_source_out, int32_t* face_part_out, void* stream);
+/* attr_out [N, channels] fp64 = a + t (b - a) per channel of attr [nv, channels] (fp32, or fp64 with attr_float64 != 0) at the end
+ * points (a, b) = edges[point_edge[p]], t = (offsets[point_plane[p]] - h_a) / (h_b - h_a): the t of nksr_slice_points, every operation
+ * rounded on its own.  One lane per (point, group of 4 channels). */
+int nksr_clip_attr(const void* attr, int attr_float64, int64_t nv, int64_t channels, const double* height, const int32_t* edges,
+                   int64_t n_edges, const double* offsets, int64_t n_planes, const int32_t* point_edge, const int32_t* point_plane,
+                   int64_t n_points, double* attr_out, void* stream);
+/* keys_out [3 nf] = (labels[f] << 32) | faces[f, k] and ids_out [3 nf] = 3 f + k for the corners of faces [nf, 3] int32 with
+ * labels [nf] >= 0; 3 nf < 2^31 */
+int nksr_clip_corner_keys(const int32_t* faces, const int32_t* labels, int64_t nf, uint64_t* keys_out, uint32_t* ids_out, void* stream);
+/* faces_out [nf, 3]: row q = the three entries of corner_vertex [3 nf] (the new vertex of every corner) of face order[q] */
+int nksr_clip_group_faces(const int32_t* order, const int32_t* corner_vertex, int64_t nf, int32_t* faces_out, void* stream);
+
 /* ---- mesh boundary loops and hole filling (nksr_amd/mesh_boundary.py: MeshBoundary; csrc/meshbound.hip) ----
  * The boundary half-edges of the topology section's edge table ordered into loops, their measures, and the faces that close them; the
  * definition is DESIGN.md section 3.16, restated in numpy by tests/mesh_boundary_ref.py.  Faces, validity and the limits as in the

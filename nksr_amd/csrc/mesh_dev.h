@@ -1,4 +1,4 @@
-// Shared by the mesh kernels (csrc/metrics.hip, csrc/meshquery.hip, csrc/meshtopo.hip, csrc/meshgeom.hip, csrc/meshsimp.hip, csrc/meshslice.hip, csrc/meshbound.hip): the reader
+// Shared by the mesh kernels (csrc/metrics.hip, csrc/meshquery.hip, csrc/meshtopo.hip, csrc/meshgeom.hip, csrc/meshsimp.hip, csrc/meshslice.hip, csrc/meshclip.hip, csrc/meshbound.hip): the reader
 // of an int32 or int64 face array (``faces_int64`` of their entry points).  What an index outside [0, nv) means is each caller's
 // business (face_corners); mesh_valid_face is the topology's notion, which the simplifier shares.  Below it what the entry points of
 // meshtopo.hip, meshgeom.hip and meshsimp.hip share on the host: mesh_check_sizes and MESH_BLOCK / MESH_LAUNCH.

@@ -10,23 +10,11 @@
 // gathers (heights per corner in the face passes, the 16-byte state of the element 2^k steps back in the ranking rounds).
 #include "common.h"
 #include "mesh_dev.h"
+#include "meshslice_dev.h"      // sl_upper, SL_LDS_OFFSETS: shared with csrc/meshclip.hip
 
 // Points, lengths and area terms are stated operation by operation: products and sums round separately, so
 // numpy gives the same bits.  The heights alone are fused, by explicit fma().
 #pragma clang fp contract(off)
-
-#define SL_LDS_OFFSETS 2048         // offsets staged in LDS up to this many planes (16 KiB)
-
-// the number of offsets <= x (offsets strictly ascending): the first plane that lies ABOVE height x
-__device__ __forceinline__ int32_t sl_upper(const double* __restrict__ o, int32_t np, double x) {
-    int32_t lo = 0, hi = np;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (o[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // ---- 1. heights ------------------------------------------------------------------------------------------------------------------
 // (a height that is not a number becomes -inf: a vertex without a position lies below every plane, for the faces and the edges alike)

@@ -66,6 +66,27 @@ class MeshingResult:
         from ..mesh_slice import MeshSlicer
         return MeshSlicer(self.v, self.f).contours(levels=levels, interval=interval, axis=axis)
 
+    def split(self, normal, offsets):
+        """``SplitMesh`` of this mesh along the planes n . x = offsets[j] (``MeshClipper.split``, nksr_amd/mesh_clip.py): one conforming
+        mesh whose faces are cut along the planes, ``c`` interpolated at the cut points; ``.parts()`` explodes it."""
+        from ..mesh_clip import MeshClipper
+        return MeshClipper(self.v, self.f, self.c).split(normal, offsets)
+
+    def clip(self, normal, offset, keep='above'):
+        """A new ``MeshingResult``: the side of the plane n . x = offset that ``keep`` names (``MeshClipper.clip``); no cap."""
+        from ..mesh_clip import MeshClipper
+        return MeshClipper(self.v, self.f, self.c).clip(normal, offset, keep)
+
+    def clip_box(self, lo, hi):
+        """A new ``MeshingResult``: what lies inside the box [lo, hi) (``MeshClipper.clip_box``)."""
+        from ..mesh_clip import MeshClipper
+        return MeshClipper(self.v, self.f, self.c).clip_box(lo, hi)
+
+    def tiles(self, tile_size, origin=(0.0, 0.0), axes=(0, 1)):
+        """``Tiles`` of this mesh on a grid of ``tile_size`` along ``axes`` (``MeshClipper.tiles``): neighbours meet without cracks."""
+        from ..mesh_clip import MeshClipper
+        return MeshClipper(self.v, self.f, self.c).tiles(tile_size, origin, axes)
+
     def boundary_loops(self):
         """``BoundaryLoops`` of this mesh (``MeshBoundary.loops``, nksr_amd/mesh_boundary.py): the boundary edges ordered into loops
         with their edge counts, lengths, areas, centroids and boxes."""

@@ -283,6 +283,32 @@ class MeshSlicer:
                         polyline_area=poly_area, plane_length=plane_length, plane_area=plane_area, plane_open=plane_open,
                         plane_polyline_start=plane_poly_start)
 
+    def interval_levels(self, interval, axis, origin=0.0):
+        """[n] fp64 numpy: the levels origin + k interval (k an integer) in (min, max] of the coordinate ``axis`` over the referenced
+        vertices (two host reads); what ``contours(interval=)`` cuts at, and ``MeshClipper.tiles``."""
+        try:
+            step, origin = float(interval), float(origin)
+        except (TypeError, ValueError):
+            raise ValueError('interval must be a positive finite number, got %r' % (interval,))
+        if not (step > 0.0 and math.isfinite(step) and math.isfinite(origin)):
+            raise ValueError('interval must be a positive finite number, got %r' % (interval,))
+        levels = np.zeros(0, np.float64)
+        if self.topology.referenced_vertices:
+            ref = self.topology.vertex_ref.bool()
+            z = self.x[:, axis].to(torch.float64)
+            lo = float(torch.where(ref, z, z.new_full((), math.inf)).amin().item())
+            hi = float(torch.where(ref, z, z.new_full((), -math.inf)).amax().item())
+            if not (math.isfinite(lo) and math.isfinite(hi)):
+                raise ValueError('contours: non-finite coordinates along axis %d' % axis)
+            k0, k1 = math.floor((lo - origin) / step) - 1, math.floor((hi - origin) / step) + 1
+            if k1 - k0 > 1 << 24:
+                raise ValueError('interval %r gives %d levels, at most 2^24' % (interval, k1 - k0))
+            levels = np.arange(k0, k1 + 1, dtype=np.float64) * step
+            if origin != 0.0:
+                levels = origin + levels
+            levels = levels[(levels > lo) & (levels <= hi)]
+        return levels
+
     def contours(self, levels=None, interval=None, axis=2):
         """``slice`` with normal = +e_axis: at ``levels``, or at the multiples of ``interval`` in (min h, max h] over the referenced
         vertices (two more host reads).  Exactly one of the two."""
@@ -293,23 +319,5 @@ class MeshSlicer:
         normal = [0.0, 0.0, 0.0]
         normal[axis] = 1.0
         if levels is None:
-            try:
-                step = float(interval)
-            except (TypeError, ValueError):
-                raise ValueError('interval must be a positive finite number, got %r' % (interval,))
-            if not (step > 0.0 and math.isfinite(step)):
-                raise ValueError('interval must be a positive finite number, got %r' % (interval,))
-            levels = np.zeros(0, np.float64)
-            if self.topology.referenced_vertices:
-                ref = self.topology.vertex_ref.bool()
-                z = self.x[:, axis].to(torch.float64)
-                lo = float(torch.where(ref, z, z.new_full((), math.inf)).amin().item())
-                hi = float(torch.where(ref, z, z.new_full((), -math.inf)).amax().item())
-                if not (math.isfinite(lo) and math.isfinite(hi)):
-                    raise ValueError('contours: non-finite coordinates along axis %d' % axis)
-                k0, k1 = math.floor(lo / step) - 1, math.floor(hi / step) + 1
-                if k1 - k0 > 1 << 24:
-                    raise ValueError('interval %r gives %d levels, at most 2^24' % (interval, k1 - k0))
-                levels = np.arange(k0, k1 + 1, dtype=np.float64) * step
-                levels = levels[(levels > lo) & (levels <= hi)]
+            levels = self.interval_levels(interval, axis)
         return self.slice(normal, levels)

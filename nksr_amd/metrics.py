@@ -24,6 +24,7 @@ from .mesh_query import MeshQuery, mesh_occupancy  # noqa: F401  (re-exported: n
 from .mesh_geometry import MeshGeometry  # noqa: F401  (re-exported: nksr.metrics.MeshGeometry)
 from .mesh_simplify import MeshSimplifier  # noqa: F401  (re-exported: nksr.metrics.MeshSimplifier)
 from .mesh_boundary import MeshBoundary  # noqa: F401  (re-exported: nksr.metrics.MeshBoundary)
+from .mesh_clip import MeshClipper  # noqa: F401  (re-exported: nksr.metrics.MeshClipper)
 from .mesh_slice import MeshSlicer  # noqa: F401  (re-exported: nksr.metrics.MeshSlicer)
 from .mesh_topology import MeshTopology  # noqa: F401  (re-exported: nksr.metrics.MeshTopology)
 from .neighbours import PointGrid, PointPyramid, choose_cell_size
