@@ -24,7 +24,7 @@ the neighbour search the package already runs for its normals, its SDF ground tr
 """
 import torch
 
-from . import ops
+from . import cloud_input, ops
 from ._lib import call, ptr, require_gpu, stream
 from .neighbours import MAX_K, _RINGS, PointGrid, PointPyramid, _grid_args, choose_cell_size, search_every_scale
 from .orient import OrientedNormals, estimate_normals, orient_graph, orient_normals  # noqa: F401  (part of this module's surface)
@@ -37,11 +37,9 @@ from .svh import inv_w0_f32
 
 
 def _check_points(xyz, cell, what='xyz'):
-    """float32 contiguous [N, 3] on the GPU, finite, |x| / cell below 2^20 -- the checks of ``svh._check_xyz`` (one readback)."""
-    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
-        raise RuntimeError('%s must be a floating-point [N,3] tensor' % what)
-    require_gpu(xyz.device)
-    xyz = xyz.to(torch.float32).contiguous()
+    """``cloud_input.points`` that a grid of ``cell`` can hold: finite, |x| / cell below 2^20 -- the checks of ``svh._check_xyz`` (one
+    readback)."""
+    xyz = cloud_input.points(xyz, None, what)
     if xyz.shape[0]:
         amax = float(xyz.abs().max())
         if not (amax * inv_w0_f32(cell) < (1 << 20) - 8):            # also catches NaN / inf
@@ -51,8 +49,8 @@ def _check_points(xyz, cell, what='xyz'):
 
 
 def _amax(xyz):
-    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
-        raise RuntimeError('xyz must be a floating-point [N,3] tensor')
+    """max |x| of a cloud in the dtype it came in (the grid's cell is chosen from it), RuntimeError unless finite"""
+    cloud_input.rows3(xyz, None)
     require_gpu(xyz.device)
     amax = float(xyz.abs().max()) if xyz.shape[0] else 0.0
     if not amax < float('inf'):
@@ -89,9 +87,7 @@ class CloudIndex:
 
     def _ranks(self, pg):
         """sorted position of every (caller-order) point in grid ``pg``"""
-        rank = torch.empty(self.n, dtype=torch.int32, device=self.device)
-        rank[pg.perm] = torch.arange(self.n, dtype=torch.int32, device=self.device)
-        return rank
+        return pg.to_caller(torch.arange(self.n, dtype=torch.int32, device=self.device))
 
     # ---- k nearest neighbours ------------------------------------------------------------------------------------------------
     def knn(self, k, query=None, exclude_self=False):
@@ -169,9 +165,7 @@ class CloudIndex:
     def radius_count(self, radius, query=None, cap=None, exclude_self=False):
         """-> int32 [Q]: the number of cloud points within ``radius`` of every query (``query=None``: of every point of the cloud,
         itself counted unless ``exclude_self``).  ``cap``: counting stops there, the result is min(count, cap)."""
-        radius = float(radius)
-        if not (0.0 < radius < float('inf')):
-            raise ValueError('radius_count: radius must be positive and finite (got %r)' % radius)
+        radius = cloud_input.positive(radius, 'radius_count', 'radius')
         ex = bool(exclude_self)
         if ex and query is not None:
             raise ValueError('radius_count: exclude_self needs query=None (the cloud itself)')
@@ -187,11 +181,7 @@ class CloudIndex:
         cnt = torch.empty(nq, dtype=torch.int32, device=dev)
         call('nksr_radius_count', ptr(g.xyz), self.n, *_grid_args(g), ptr(q), nq, radius, int(cap) if cap is not None else 0, int(ex), None,
              ptr(cnt), stream())
-        if query is not None:
-            return cnt
-        out = torch.empty_like(cnt)
-        out[g.perm] = cnt
-        return out
+        return cnt if query is not None else g.to_caller(cnt)
 
     # ---- clusters --------------------------------------------------------------------------------------------------------------
     def cluster_dbscan(self, eps, min_points):
@@ -210,9 +200,7 @@ class CloudIndex:
     def bbox_centre(self):
         """float64 numpy [3]: the centre of the cloud's bounding box (the point the registration sums are taken about)."""
         if self._centre is None:
-            from .density import bbox_center
-            lo, hi, _ = bbox_center(self.xyz)
-            self._centre = 0.5 * (lo.double() + hi.double()).cpu().numpy()
+            self._centre = cloud_input.bbox_centre64(self.xyz)
         return self._centre
 
     def compute_fpfh_feature(self, normal, radius, max_nn=32):
@@ -272,9 +260,7 @@ def voxel_downsample(xyz, voxel_size, normal=None, sensor=None, color=None, redu
     the voxel, with its own attributes.  -> ``VoxelDownsample``."""
     if reduce not in ('mean', 'nearest'):
         raise ValueError("voxel_downsample: reduce must be 'mean' or 'nearest' (got %r)" % (reduce,))
-    voxel_size = float(voxel_size)
-    if not (0.0 < voxel_size < float('inf')):
-        raise ValueError('voxel_downsample: voxel_size must be positive and finite (got %r)' % voxel_size)
+    voxel_size = cloud_input.positive(voxel_size, 'voxel_downsample', 'voxel_size')
     xyz = _check_points(xyz, voxel_size)
     n, dev = xyz.shape[0], xyz.device
     given = [(name, a) for name, a in (('normal', normal), ('sensor', sensor), ('color', color)) if a is not None]

@@ -15,14 +15,13 @@
 //                      partial answers of a row meet in ONE 64-bit integer atomicMin on (bits of D) << 32 | b.  D is a sum of squares,
 //                      never negative, so its bit pattern orders as an unsigned integer and the minimum is the smallest D, then the
 //                      smallest b: independent of the order the workgroups run in.  k_feature_match_finish unpacks the keys.
-//   k_pose_score       nksr_pose_score: all hypotheses in one launch, laid out as k_plane_score (csrc/segment.hip): a workgroup holds
-//                      PO_CHUNK transforms in LDS (96 B each), a lane PO_PAIRS pairs in registers; ballot + popcount per wavefront
-//                      into integer LDS counters, one integer atomicAdd per (workgroup, hypothesis).
+//   PoseModel          nksr_pose_score: all hypotheses in one launch of k_hypothesis_score (score_dev.h), the scorer csrc/segment.hip
+//                      runs on planes: integer counts, -1 for a transform that is not finite.
 //   k_corr_accumulate  nksr_corr_accumulate: the inlier mask of ONE transform and the point-method rows of the ICP sums over its
-//                      inliers (icp_dev.h: the same transform, the same terms), reduced in the fixed order of csrc/register.hip.
+//                      inliers (icp_dev.h: the same transform, the same terms, the same block_row_sums).
 #include "common.h"
 #include "icp_dev.h"
-#include "wave_dev.h"
+#include "score_dev.h"
 
 // ---- A. feature matching -------------------------------------------------------------------------------------------------------------
 #define FM_BLOCK 256
@@ -113,11 +112,6 @@ extern "C" int nksr_feature_match(const float* A, int64_t na, const float* B, in
 }
 
 // ---- B. pose hypotheses ----------------------------------------------------------------------------------------------------------------
-#define PO_BLOCK 256
-#define PO_WAVES (PO_BLOCK / NKSR_WAVE)
-#define PO_PAIRS 2                  // pairs a lane keeps in registers (6 floats + 6 doubles)
-#define PO_CHUNK 64                 // transforms a workgroup keeps in LDS (6 KB) and counts (1 KB)
-
 // e = (R p + t) - q, |e|^2 <= t2; moved [3] = R p + t
 __device__ __forceinline__ bool pose_inlier(const double* __restrict__ T, const float p[3], const double q[3], double t2, double moved[3]) {
 #pragma clang fp contract(off)
@@ -133,54 +127,37 @@ __device__ __forceinline__ bool pose_not_finite(const double* __restrict__ T) {
     return !finite;
 }
 
-__global__ void __launch_bounds__(PO_BLOCK) k_pose_score(const float* __restrict__ src, const float* __restrict__ tgt, int64_t n,
-                                                         const double* __restrict__ transforms, int n_hyp, double t2, int32_t* counts) {
-    __shared__ double s_T[PO_CHUNK * 12];
-    __shared__ int32_t s_count[PO_WAVES][PO_CHUNK];
-    const int h0 = blockIdx.y * PO_CHUNK;
-    const int nh = n_hyp - h0 < PO_CHUNK ? n_hyp - h0 : PO_CHUNK;
-    for (int k = threadIdx.x; k < nh * 12; k += PO_BLOCK) s_T[k] = transforms[(int64_t)h0 * 12 + k];
-    float p[PO_PAIRS][3];
-    double q[PO_PAIRS][3];
-#pragma unroll
-    for (int k = 0; k < PO_PAIRS; ++k) {
-        const int64_t i = ((int64_t)blockIdx.x * PO_PAIRS + k) * PO_BLOCK + threadIdx.x;
-        const bool on = i < n;
+// the model of k_hypothesis_score (score_dev.h): 2 pairs a lane (6 floats + 6 doubles), 64 transforms a workgroup (6 KB, and 1 KB of
+// counts); the threshold arrives squared
+struct PoseModel {
+    static constexpr int WIDTH = 12, ITEMS = 2, CHUNK = 64, MAX_H = NKSR_POSE_MAX_H;
+    static constexpr const char* N_NAME = "n_pairs";
+    static constexpr const char* H_NAME = "n_hyp";
+    struct Items {
+        const float* __restrict__ src;
+        const float* __restrict__ tgt;
+        bool missing() const { return !src || !tgt; }
+    };
+    struct Item { float p[3]; double q[3]; };
+    static __device__ __forceinline__ void load(const Items& in, int64_t i, bool on, Item& it) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            p[k][a] = on ? src[i * 3 + a] : 0.f;
-            q[k][a] = on ? (double)tgt[i * 3 + a] : (double)NAN;          // a lane past the end carries a NaN: no comparison with it holds
+            it.p[a] = on ? in.src[i * 3 + a] : 0.f;
+            it.q[a] = on ? (double)in.tgt[i * 3 + a] : (double)NAN;         // a lane past the end carries a NaN: no comparison with it holds
         }
     }
-    __syncthreads();
-    const int wave = threadIdx.x / NKSR_WAVE, lane = threadIdx.x % NKSR_WAVE;
-    for (int h = 0; h < nh; ++h) {
-        int cnt = 0;
-#pragma unroll
-        for (int k = 0; k < PO_PAIRS; ++k) {
-            double moved[3];
-            cnt += __popcll(__ballot(pose_inlier(s_T + 12 * h, p[k], q[k], t2, moved)));
-        }
-        if (lane == 0) s_count[wave][h] = cnt;
+    static __device__ __forceinline__ bool inlier(const double* T, const Item& it, double t2) {
+        double moved[3];
+        return pose_inlier(T, it.p, it.q, t2, moved);
     }
-    __syncthreads();
-    for (int h = threadIdx.x; h < nh; h += PO_BLOCK) {
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < PO_WAVES; ++w) total += s_count[w][h];
-        if (pose_not_finite(s_T + 12 * h)) total = blockIdx.x == 0 ? -1 : 0;          // (the counts start at 0: -1 in the end)
-        if (total) atomicAdd(counts + h0 + h, total);
-    }
-}
+    static __device__ __forceinline__ bool degenerate(const double* T) { return pose_not_finite(T); }
+};
 
-#define CA_WAVES (NKSR_ICP_BLOCK / NKSR_WAVE)
 #define CA_FIELDS (NKSR_ICP_PT_PQ + 9)          // the fields the point method fills
-static_assert(CA_FIELDS <= NKSR_ICP_FIELDS && NKSR_ICP_FIELDS <= NKSR_ICP_BLOCK, "a row nksr_icp_reduce takes, one lane per field at the end");
 
 __global__ void __launch_bounds__(NKSR_ICP_BLOCK) k_corr_accumulate(const float* __restrict__ src, const float* __restrict__ tgt, int64_t n,
                                                                     const double* __restrict__ T, const double* __restrict__ centre, double t2,
                                                                     uint8_t* __restrict__ mask, double* __restrict__ partials) {
-    __shared__ double s_red[CA_WAVES][NKSR_ICP_FIELDS];
     const int64_t i = (int64_t)blockIdx.x * NKSR_ICP_BLOCK + threadIdx.x;
     double term[NKSR_ICP_FIELDS];
 #pragma unroll
@@ -197,47 +174,17 @@ __global__ void __launch_bounds__(NKSR_ICP_BLOCK) k_corr_accumulate(const float*
         }
     }
     // every lane of the block from here on (lanes past the end and outliers carry zeros)
-    const int wave = threadIdx.x / NKSR_WAVE, lane = threadIdx.x % NKSR_WAVE;
-#pragma unroll
-    for (int f = 0; f < CA_FIELDS; ++f) {
-        const double v = wave_sum_f64(term[f]);
-        if (lane == 0) s_red[wave][f] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < NKSR_ICP_FIELDS) {
-        double v = 0.0;
-        if ((int)threadIdx.x < CA_FIELDS)
-            for (int w = 0; w < CA_WAVES; ++w) v += s_red[w][threadIdx.x];
-        partials[(int64_t)blockIdx.x * NKSR_ICP_FIELDS + threadIdx.x] = v;
-    }
-}
-
-static int pose_args(const char* who, int64_t n, double threshold) {
-    if (n < 0 || n >= (1ll << 31)) return nksr_set_error(NKSR_ERR_ARG, "%s: n_pairs=%lld outside [0, 2^31)", who, (long long)n);
-    if (!(threshold >= 0.0) || !(threshold < (double)INFINITY))
-        return nksr_set_error(NKSR_ERR_ARG, "%s: the distance threshold must be finite and not negative", who);
-    return NKSR_OK;
+    block_row_sums<CA_FIELDS, NKSR_ICP_FIELDS>(term, partials);
 }
 
 extern "C" int nksr_pose_score(const float* src, const float* tgt, int64_t n_pairs, const double* transforms, int64_t n_hyp, double threshold,
                                int32_t* counts_out, void* stream) {
-    if (int rc = pose_args("pose score", n_pairs, threshold)) return rc;
-    if (n_hyp < 0 || n_hyp > NKSR_POSE_MAX_H)
-        return nksr_set_error(NKSR_ERR_ARG, "pose score: n_hyp=%lld outside [0, %d]", (long long)n_hyp, NKSR_POSE_MAX_H);
-    if (n_hyp == 0) return NKSR_OK;
-    if (!transforms || !counts_out || (n_pairs > 0 && (!src || !tgt))) return nksr_set_error(NKSR_ERR_ARG, "pose score: NULL arrays");
-    hipStream_t st = (hipStream_t)stream;
-    NKSR_CHECK_HIP(hipMemsetAsync(counts_out, 0, sizeof(int32_t) * (size_t)n_hyp, st));
-    // (n_pairs = 0: one column of workgroups still marks the transforms that are not finite)
-    const dim3 grid(n_pairs > 0 ? nksr_blocks(n_pairs, PO_BLOCK * PO_PAIRS) : 1, nksr_blocks(n_hyp, PO_CHUNK));
-    hipLaunchKernelGGL(k_pose_score, grid, dim3(PO_BLOCK), 0, st, src, tgt, n_pairs, transforms, (int)n_hyp, threshold * threshold, counts_out);
-    NKSR_CHECK_LAUNCH();
-    return NKSR_OK;
+    return hypothesis_score<PoseModel>("pose score", {src, tgt}, n_pairs, transforms, n_hyp, threshold, threshold * threshold, counts_out, stream);
 }
 
 extern "C" int nksr_corr_accumulate(const float* src, const float* tgt, int64_t n_pairs, const double* transform, const double* centre,
                                     double threshold, uint8_t* mask_out, double* partials_out, void* stream) {
-    if (int rc = pose_args("corr accumulate", n_pairs, threshold)) return rc;
+    if (int rc = threshold_args("corr accumulate", "n_pairs", n_pairs, threshold)) return rc;
     if (n_pairs == 0) return NKSR_OK;
     if (!src || !tgt || !transform || !centre || !mask_out || !partials_out) return nksr_set_error(NKSR_ERR_ARG, "corr accumulate: NULL arrays");
     hipLaunchKernelGGL(k_corr_accumulate, dim3(nksr_blocks(n_pairs, NKSR_ICP_BLOCK)), dim3(NKSR_ICP_BLOCK), 0, (hipStream_t)stream, src, tgt,

@@ -1,8 +1,37 @@
 // The terms of one ICP correspondence, shared by the kernels that write rows of NKSR_ICP_FIELDS sums (csrc/register.hip: pairs found
 // by a search; csrc/global_register.hip: pairs that are given): the transform and the terms are stated ONCE, formed without fused
 // multiply-adds in the order include/nksr_hip.h gives.
+//
+// block_row_sums is the end of every kernel that writes such a row (k_icp_accumulate, k_corr_accumulate, and k_plane_moments of
+// csrc/segment.hip): THE statement of the order in which a workgroup adds its lanes' terms.
 #pragma once
 #include "common.h"
+#include "wave_dev.h"
+
+static_assert(NKSR_ICP_BLOCK % NKSR_WAVE == 0 && NKSR_ICP_FIELDS <= NKSR_ICP_BLOCK, "whole wavefronts, one lane per field at the end");
+
+// term[0 .. NF) of the NKSR_ICP_BLOCK lanes of the workgroup -> row blockIdx.x of partials, NKSR_ICP_FIELDS wide, zero above NF.  Per
+// field: the 64 lanes of a wavefront by the butterfly of wave_sum_f64 (xor 32, 16, ... 1), then the wavefronts in wave order starting
+// from 0.0.  Every lane of the workgroup must call it (a lane without an item carries zeros).  STRIDE: the width of the LDS rows.
+template <int NF, int STRIDE = NF>
+__device__ __forceinline__ void block_row_sums(const double* term, double* __restrict__ partials) {
+    static_assert(NF <= STRIDE && STRIDE <= NKSR_ICP_FIELDS, "the fields of one row");
+    constexpr int WAVES = NKSR_ICP_BLOCK / NKSR_WAVE;
+    __shared__ double s_red[WAVES][STRIDE];
+    const int wave = threadIdx.x / NKSR_WAVE, lane = threadIdx.x % NKSR_WAVE;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const double v = wave_sum_f64(term[f]);
+        if (lane == 0) s_red[wave][f] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < NKSR_ICP_FIELDS) {
+        double v = 0.0;
+        if ((int)threadIdx.x < NF)
+            for (int w = 0; w < WAVES; ++w) v += s_red[w][threadIdx.x];
+        partials[(int64_t)blockIdx.x * NKSR_ICP_FIELDS + threadIdx.x] = v;
+    }
+}
 
 // p = R s + t, every product and sum rounded on its own
 __device__ __forceinline__ void icp_transform(const double* __restrict__ T, const float s[3], double p[3]) {

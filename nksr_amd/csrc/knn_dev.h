@@ -82,3 +82,14 @@ static int knn_grid_args(const char* who, const float* xyz_sorted, const int32_t
     if (!(cell > 0.f) || !(inv_cell > 0.f)) return nksr_set_error(NKSR_ERR_ARG, "%s: cell and inv_cell must be > 0", who);
     return NKSR_OK;
 }
+
+// a search within `radius` on the 27 cells of a grid: the radius, the grid, and a cell that covers the radius.  `empty`: the caller has
+// nothing to search for and returns after its own checks -- the grid is not looked at
+static int radius_grid_args(const char* who, const float* xyz_sorted, const int32_t* start, const int32_t* end, const int64_t* hkeys,
+                            const int32_t* hvals, int32_t hcap, float cell, float inv_cell, float radius, bool empty = false) {
+    if (!(radius > 0.f) || !(radius < 3.4e38f)) return nksr_set_error(NKSR_ERR_ARG, "%s: radius must be positive and finite", who);
+    if (empty) return NKSR_OK;
+    if (int rc = knn_grid_args(who, xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell)) return rc;
+    if (!(cell >= radius)) return nksr_set_error(NKSR_ERR_ARG, "%s: the grid's cell (%g) must be >= radius (%g)", who, (double)cell, (double)radius);
+    return NKSR_OK;
+}

@@ -162,9 +162,7 @@ extern "C" int nksr_radius_count(const float* xyz_sorted, int64_t n_ref, const i
                                  const int32_t* hvals, int32_t hcap, float cell, float inv_cell, const float* query, int64_t nq, float radius,
                                  int32_t cap, int exclude_self, const int32_t* self_index, int32_t* count_out, void* stream) {
     if (nq < 0 || n_ref < 0) return nksr_set_error(NKSR_ERR_ARG, "radius count: negative size (nq=%lld, n_ref=%lld)", (long long)nq, (long long)n_ref);
-    if (!(radius > 0.f) || !(radius < 3.4e38f)) return nksr_set_error(NKSR_ERR_ARG, "radius count: radius must be positive and finite");
-    if (int rc = knn_grid_args("radius count", xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell)) return rc;
-    if (!(cell >= radius)) return nksr_set_error(NKSR_ERR_ARG, "radius count: the grid's cell (%g) must be >= radius (%g)", (double)cell, (double)radius);
+    if (int rc = radius_grid_args("radius count", xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell, radius)) return rc;
     if (!query && nq > n_ref) return nksr_set_error(NKSR_ERR_ARG, "radius count: query NULL (the cloud itself) with nq = %lld > n_ref = %lld", (long long)nq, (long long)n_ref);
     if (nq > 0 && !count_out) return nksr_set_error(NKSR_ERR_ARG, "radius count: NULL output array");
     if (nq == 0) return NKSR_OK;

@@ -218,13 +218,11 @@ extern "C" int nksr_mls_project(const float* xyz_sorted, int64_t n_ref, const in
                                 double* mean_curvature_out, double* gaussian_curvature_out, double* variation_out, int32_t* count_out,
                                 int8_t* order_used_out, void* stream) {
     if (nq < 0 || n_ref < 0) return nksr_set_error(NKSR_ERR_ARG, "mls project: negative size (nq=%lld, n_ref=%lld)", (long long)nq, (long long)n_ref);
-    if (!(radius > 0.f) || !(radius < 3.4e38f)) return nksr_set_error(NKSR_ERR_ARG, "mls project: radius must be positive and finite");
+    if (int rc = radius_grid_args("mls project", xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell, radius)) return rc;
     if (!(sigma > 0.0) || !(sigma < 1.7e308)) return nksr_set_error(NKSR_ERR_ARG, "mls project: sigma must be positive and finite");
     if (order != 1 && order != 2) return nksr_set_error(NKSR_ERR_ARG, "mls project: order must be 1 or 2 (got %d)", order);
     if (min_neighbors < (order == 1 ? 3 : 6))
         return nksr_set_error(NKSR_ERR_ARG, "mls project: min_neighbors must be >= %d at order %d (got %d)", order == 1 ? 3 : 6, order, min_neighbors);
-    if (int rc = knn_grid_args("mls project", xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell)) return rc;
-    if (!(cell >= radius)) return nksr_set_error(NKSR_ERR_ARG, "mls project: the grid's cell (%g) must be >= radius (%g)", (double)cell, (double)radius);
     if (!query && nq > n_ref) return nksr_set_error(NKSR_ERR_ARG, "mls project: query NULL (the cloud itself) with nq = %lld > n_ref = %lld", (long long)nq, (long long)n_ref);
     if (nq > 0 && (!position_out || !normal_out || !mean_curvature_out || !gaussian_curvature_out || !variation_out || !count_out || !order_used_out))
         return nksr_set_error(NKSR_ERR_ARG, "mls project: NULL output arrays");

@@ -16,10 +16,7 @@
 #include "common.h"
 #include "icp_dev.h"
 #include "knn_dev.h"
-#include "wave_dev.h"
 
-#define ICP_WAVES (NKSR_ICP_BLOCK / NKSR_WAVE)
-static_assert(NKSR_ICP_BLOCK % NKSR_WAVE == 0 && NKSR_ICP_FIELDS <= NKSR_ICP_BLOCK, "whole wavefronts, one lane per field at the end");
 static_assert(NKSR_ICP_PT_PQ + 9 <= NKSR_ICP_FIELDS && NKSR_ICP_PL_JJ + 21 == NKSR_ICP_PL_JR && NKSR_ICP_PL_JR + 6 == NKSR_ICP_PL_RR &&
               NKSR_ICP_PL_RR < NKSR_ICP_FIELDS, "layout of the sums");
 
@@ -29,7 +26,6 @@ __global__ void __launch_bounds__(NKSR_ICP_BLOCK) k_icp_accumulate(KnnGrid g, co
                                                                    const double* __restrict__ centre, float r2, int64_t* __restrict__ corr,
                                                                    double* __restrict__ partials) {
     constexpr int NF = METHOD == 0 ? NKSR_ICP_PT_PQ + 9 : NKSR_ICP_PL_RR + 1;          // the fields this method fills
-    __shared__ double s_red[ICP_WAVES][NKSR_ICP_FIELDS];
     const int64_t i = (int64_t)blockIdx.x * NKSR_ICP_BLOCK + threadIdx.x;
     double term[NKSR_ICP_FIELDS];
 #pragma unroll
@@ -65,19 +61,7 @@ __global__ void __launch_bounds__(NKSR_ICP_BLOCK) k_icp_accumulate(KnnGrid g, co
         }
     }
     // every lane of the block from here on (lanes past the end and lanes without a correspondence carry zeros)
-    const int wave = threadIdx.x / NKSR_WAVE, lane = threadIdx.x % NKSR_WAVE;
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-        const double v = wave_sum_f64(term[f]);
-        if (lane == 0) s_red[wave][f] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < NKSR_ICP_FIELDS) {
-        double v = 0.0;
-        if ((int)threadIdx.x < NF)
-            for (int w = 0; w < ICP_WAVES; ++w) v += s_red[w][threadIdx.x];
-        partials[(int64_t)blockIdx.x * NKSR_ICP_FIELDS + threadIdx.x] = v;
-    }
+    block_row_sums<NF, NKSR_ICP_FIELDS>(term, partials);
 }
 
 // column sums of the rows: thread t takes field t % FIELDS of the rows t / FIELDS, + slices, + 2 slices ... in row order; the
@@ -103,11 +87,9 @@ extern "C" int nksr_icp_accumulate(const float* xyz_sorted, int64_t n_ref, const
                                    const float* source, int64_t n_src, const double* transform, const double* centre, float radius, int method,
                                    int64_t* corr_out, double* partials_out, void* stream) {
     if (n_src < 0 || n_ref < 0) return nksr_set_error(NKSR_ERR_ARG, "icp accumulate: negative size (n_src=%lld, n_ref=%lld)", (long long)n_src, (long long)n_ref);
-    if (!(radius > 0.f) || !(radius < 3.4e38f)) return nksr_set_error(NKSR_ERR_ARG, "icp accumulate: radius must be positive and finite");
+    if (int rc = radius_grid_args("icp accumulate", xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell, radius, n_src == 0)) return rc;
     if (method != 0 && method != 1) return nksr_set_error(NKSR_ERR_ARG, "icp accumulate: method must be 0 (point) or 1 (plane), got %d", method);
     if (n_src == 0) return NKSR_OK;
-    if (int rc = knn_grid_args("icp accumulate", xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell)) return rc;
-    if (!(cell >= radius)) return nksr_set_error(NKSR_ERR_ARG, "icp accumulate: the grid's cell (%g) must be >= radius (%g)", (double)cell, (double)radius);
     if (!perm || !source || !transform || !centre) return nksr_set_error(NKSR_ERR_ARG, "icp accumulate: NULL perm / source / transform / centre");
     if (method == 1 && !normal_sorted) return nksr_set_error(NKSR_ERR_ARG, "icp accumulate: the plane method needs the target's normals");
     if (!corr_out || !partials_out) return nksr_set_error(NKSR_ERR_ARG, "icp accumulate: NULL output arrays");

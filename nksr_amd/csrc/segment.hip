@@ -24,15 +24,15 @@
 //
 // B. Plane RANSAC.  Residual of point (x, y, z) (fp32, widened) to plane (a, b, c, d): s = ((a x + b y) + c z) + d in fp64, every
 //    product and sum rounded on its own (no fused multiply-add); inlier iff |s| <= t.
-//    k_plane_score    all H hypotheses in one launch: a workgroup holds PS_CHUNK hypotheses in LDS (32 B each), a lane holds PS_POINTS
-//                     points in registers and loops over the hypotheses; ballot + popcount per wavefront into integer LDS counters,
-//                     one integer atomicAdd per (workgroup, hypothesis) at the end.  Integer sums do not depend on the order.
+//    PlaneModel       nksr_plane_score: all H hypotheses in one launch of k_hypothesis_score (score_dev.h), integer counts.
 //                     A hypothesis that is not finite or whose normal is zero is degenerate: its count is -1.
 //    k_plane_moments  the inlier mask of ONE plane and, per workgroup, the fp64 sums of 1, x'_a and x'_a x'_b (a <= b) over the inliers,
-//                     x' = x - centre: rows NKSR_ICP_FIELDS wide, reduced in the fixed order of register.hip (wavefront butterfly,
-//                     waves in order; then nksr_icp_reduce over the rows).  No atomics.
+//                     x' = x - centre: rows NKSR_ICP_FIELDS wide, reduced in the fixed order of block_row_sums (icp_dev.h; then
+//                     nksr_icp_reduce over the rows).  No atomics.
 #include "common.h"
+#include "icp_dev.h"
 #include "knn_dev.h"
+#include "score_dev.h"
 #include "uf_dev.h"
 #include "wave_dev.h"
 
@@ -123,11 +123,7 @@ __global__ void __launch_bounds__(DB_BLOCK) k_dbscan_border(KnnGrid g, int64_t n
 static int dbscan_args(const char* who, const float* xyz_sorted, int64_t n, const int32_t* start, const int32_t* end, const int64_t* hkeys,
                        const int32_t* hvals, int32_t hcap, float cell, float inv_cell, float radius) {
     if (n < 0 || n >= (1ll << 31)) return nksr_set_error(NKSR_ERR_ARG, "%s: n=%lld outside [0, 2^31)", who, (long long)n);
-    if (!(radius > 0.f) || !(radius < 3.4e38f)) return nksr_set_error(NKSR_ERR_ARG, "%s: radius must be positive and finite", who);
-    if (n == 0) return NKSR_OK;
-    if (int rc = knn_grid_args(who, xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell)) return rc;
-    if (!(cell >= radius)) return nksr_set_error(NKSR_ERR_ARG, "%s: the grid's cell (%g) must be >= radius (%g)", who, (double)cell, (double)radius);
-    return NKSR_OK;
+    return radius_grid_args(who, xyz_sorted, start, end, hkeys, hvals, hcap, cell, inv_cell, radius, n == 0);
 }
 
 extern "C" int nksr_dbscan_components(const float* xyz_sorted, int64_t n, const int32_t* start, const int32_t* end, const int64_t* hkeys,
@@ -172,12 +168,6 @@ extern "C" int nksr_dbscan_border(const float* xyz_sorted, int64_t n, const int3
 }
 
 // ---- B. plane RANSAC ---------------------------------------------------------------------------------------------------------------
-#define PS_BLOCK 256
-#define PS_WAVES (PS_BLOCK / NKSR_WAVE)
-#define PS_POINTS 4                 // points a lane keeps in registers (12 doubles)
-#define PS_CHUNK 128                // hypotheses a workgroup keeps in LDS (4 KB) and counts (2 KB)
-#define PS_MAX_H (1 << 20)
-
 __device__ __forceinline__ double plane_residual(const double* __restrict__ p, double x, double y, double z) {
 #pragma clang fp contract(off)
     const double u = p[0] * x + p[1] * y;
@@ -189,48 +179,33 @@ __device__ __forceinline__ bool plane_degenerate(const double* __restrict__ p) {
     return !finite || (p[0] == 0.0 && p[1] == 0.0 && p[2] == 0.0);
 }
 
-__global__ void __launch_bounds__(PS_BLOCK) k_plane_score(const float* __restrict__ xyz, int64_t n, const double* __restrict__ planes, int n_planes,
-                                                          double t, int32_t* counts) {
-    __shared__ double s_plane[PS_CHUNK * 4];
-    __shared__ int32_t s_count[PS_WAVES][PS_CHUNK];
-    const int h0 = blockIdx.y * PS_CHUNK;
-    const int nh = n_planes - h0 < PS_CHUNK ? n_planes - h0 : PS_CHUNK;
-    for (int k = threadIdx.x; k < nh * 4; k += PS_BLOCK) s_plane[k] = planes[(int64_t)h0 * 4 + k];
-    double x[PS_POINTS], y[PS_POINTS], z[PS_POINTS];
-#pragma unroll
-    for (int k = 0; k < PS_POINTS; ++k) {
-        const int64_t i = ((int64_t)blockIdx.x * PS_POINTS + k) * PS_BLOCK + threadIdx.x;
-        const bool on = i < n;
-        x[k] = on ? (double)xyz[i * 3] : (double)NAN;           // a lane past the end carries a NaN: no comparison with it holds
-        y[k] = on ? (double)xyz[i * 3 + 1] : (double)NAN;
-        z[k] = on ? (double)xyz[i * 3 + 2] : (double)NAN;
+// the model of k_hypothesis_score (score_dev.h): 4 points a lane (12 doubles), 128 planes a workgroup (4 KB, and 2 KB of counts)
+struct PlaneModel {
+    static constexpr int WIDTH = 4, ITEMS = 4, CHUNK = 128, MAX_H = 1 << 20;
+    static constexpr const char* N_NAME = "n";
+    static constexpr const char* H_NAME = "n_planes";
+    struct Items {
+        const float* __restrict__ xyz;
+        bool missing() const { return !xyz; }
+    };
+    struct Item { double x, y, z; };
+    static __device__ __forceinline__ void load(const Items& in, int64_t i, bool on, Item& p) {
+        p.x = on ? (double)in.xyz[i * 3] : (double)NAN;           // a lane past the end carries a NaN: no comparison with it holds
+        p.y = on ? (double)in.xyz[i * 3 + 1] : (double)NAN;
+        p.z = on ? (double)in.xyz[i * 3 + 2] : (double)NAN;
     }
-    __syncthreads();
-    const int wave = threadIdx.x / NKSR_WAVE, lane = threadIdx.x % NKSR_WAVE;
-    for (int h = 0; h < nh; ++h) {
-        int cnt = 0;
-#pragma unroll
-        for (int k = 0; k < PS_POINTS; ++k) cnt += __popcll(__ballot(fabs(plane_residual(s_plane + 4 * h, x[k], y[k], z[k])) <= t));
-        if (lane == 0) s_count[wave][h] = cnt;
+    static __device__ __forceinline__ bool inlier(const double* plane, const Item& p, double t) {
+        return fabs(plane_residual(plane, p.x, p.y, p.z)) <= t;
     }
-    __syncthreads();
-    for (int h = threadIdx.x; h < nh; h += PS_BLOCK) {
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < PS_WAVES; ++w) total += s_count[w][h];
-        if (plane_degenerate(s_plane + 4 * h)) total = blockIdx.x == 0 ? -1 : 0;           // (the counts start at 0: -1 in the end)
-        if (total) atomicAdd(counts + h0 + h, total);
-    }
-}
+    static __device__ __forceinline__ bool degenerate(const double* plane) { return plane_degenerate(plane); }
+};
 
-#define PM_WAVES (NKSR_ICP_BLOCK / NKSR_WAVE)
-static_assert(NKSR_PLANE_MOMENT + 6 == NKSR_PLANE_FIELDS && NKSR_PLANE_FIELDS <= NKSR_ICP_FIELDS && NKSR_ICP_FIELDS <= NKSR_ICP_BLOCK,
+static_assert(NKSR_PLANE_MOMENT + 6 == NKSR_PLANE_FIELDS && NKSR_PLANE_FIELDS <= NKSR_ICP_FIELDS,
               "layout of the sums inside a row nksr_icp_reduce takes");
 
 __global__ void __launch_bounds__(NKSR_ICP_BLOCK) k_plane_moments(const float* __restrict__ xyz, int64_t n, const double* __restrict__ plane,
                                                                   const double* __restrict__ centre, double t, uint8_t* __restrict__ mask,
                                                                   double* __restrict__ partials) {
-    __shared__ double s_red[PM_WAVES][NKSR_PLANE_FIELDS];
     const int64_t i = (int64_t)blockIdx.x * NKSR_ICP_BLOCK + threadIdx.x;
     double term[NKSR_PLANE_FIELDS];
 #pragma unroll
@@ -253,47 +228,17 @@ __global__ void __launch_bounds__(NKSR_ICP_BLOCK) k_plane_moments(const float* _
         }
     }
     // every lane of the block from here on (lanes past the end and outliers carry zeros)
-    const int wave = threadIdx.x / NKSR_WAVE, lane = threadIdx.x % NKSR_WAVE;
-#pragma unroll
-    for (int f = 0; f < NKSR_PLANE_FIELDS; ++f) {
-        const double v = wave_sum_f64(term[f]);
-        if (lane == 0) s_red[wave][f] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < NKSR_ICP_FIELDS) {
-        double v = 0.0;
-        if ((int)threadIdx.x < NKSR_PLANE_FIELDS)
-            for (int w = 0; w < PM_WAVES; ++w) v += s_red[w][threadIdx.x];
-        partials[(int64_t)blockIdx.x * NKSR_ICP_FIELDS + threadIdx.x] = v;
-    }
-}
-
-static int plane_args(const char* who, int64_t n, double threshold) {
-    if (n < 0 || n >= (1ll << 31)) return nksr_set_error(NKSR_ERR_ARG, "%s: n=%lld outside [0, 2^31)", who, (long long)n);
-    if (!(threshold >= 0.0) || !(threshold < (double)INFINITY))
-        return nksr_set_error(NKSR_ERR_ARG, "%s: the distance threshold must be finite and not negative", who);
-    return NKSR_OK;
+    block_row_sums<NKSR_PLANE_FIELDS>(term, partials);
 }
 
 extern "C" int nksr_plane_score(const float* xyz, int64_t n, const double* planes, int64_t n_planes, double threshold, int32_t* counts_out,
                                 void* stream) {
-    if (int rc = plane_args("plane score", n, threshold)) return rc;
-    if (n_planes < 0 || n_planes > PS_MAX_H)
-        return nksr_set_error(NKSR_ERR_ARG, "plane score: n_planes=%lld outside [0, %d]", (long long)n_planes, PS_MAX_H);
-    if (n_planes == 0) return NKSR_OK;
-    if (!planes || !counts_out || (n > 0 && !xyz)) return nksr_set_error(NKSR_ERR_ARG, "plane score: NULL arrays");
-    hipStream_t st = (hipStream_t)stream;
-    NKSR_CHECK_HIP(hipMemsetAsync(counts_out, 0, sizeof(int32_t) * (size_t)n_planes, st));
-    // (n = 0: one column of workgroups still marks the degenerate hypotheses)
-    const dim3 grid(n > 0 ? nksr_blocks(n, PS_BLOCK * PS_POINTS) : 1, nksr_blocks(n_planes, PS_CHUNK));
-    hipLaunchKernelGGL(k_plane_score, grid, dim3(PS_BLOCK), 0, st, xyz, n, planes, (int)n_planes, threshold, counts_out);
-    NKSR_CHECK_LAUNCH();
-    return NKSR_OK;
+    return hypothesis_score<PlaneModel>("plane score", {xyz}, n, planes, n_planes, threshold, threshold, counts_out, stream);
 }
 
 extern "C" int nksr_plane_moments(const float* xyz, int64_t n, const double* plane, const double* centre, double threshold, uint8_t* mask_out,
                                   double* partials_out, void* stream) {
-    if (int rc = plane_args("plane moments", n, threshold)) return rc;
+    if (int rc = threshold_args("plane moments", "n", n, threshold)) return rc;
     if (n == 0) return NKSR_OK;
     if (!xyz || !plane || !centre || !mask_out || !partials_out) return nksr_set_error(NKSR_ERR_ARG, "plane moments: NULL arrays");
     hipLaunchKernelGGL(k_plane_moments, dim3(nksr_blocks(n, NKSR_ICP_BLOCK)), dim3(NKSR_ICP_BLOCK), 0, (hipStream_t)stream, xyz, n, plane, centre,

@@ -13,7 +13,7 @@ of different sessions -- and hands it to the ICP.
     fp32 differences, the lowest index on a tie).
   * ``registration_ransac_based_on_feature_matching``: index triples drawn on the host (``draw_triples``), rejected where their edge
     lengths disagree (``edge_length_keep``), fitted by batched Kabsch in fp64 numpy (``fit_triples``); ALL surviving poses scored on the
-    device (``k_pose_score``: integer counts), the best refitted once on its inliers (``k_corr_accumulate`` + ``nksr_icp_reduce`` +
+    device (``k_hypothesis_score`` of csrc/score_dev.h: integer counts), the best refitted once on its inliers (``k_corr_accumulate`` + ``nksr_icp_reduce`` +
     ``register.kabsch_step``).
   * ``register_global``: voxel downsampling, features, RANSAC and point-to-plane ICP in one call.
 ``draw_triples``, ``edge_length_keep`` and ``fit_triples`` are plain numpy and need no GPU.  Everything else: GPU tensors only.
@@ -21,11 +21,10 @@ of different sessions -- and hands it to the ICP.
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, cloud_input
 from ._lib import call, ptr, require_gpu, stream
 
 BINS, MAX_K = _lib.FPFH_BINS, _lib.FPFH_MAX_K
-FIELDS, BLOCK = _lib.ICP_FIELDS, _lib.ICP_BLOCK
 MATCH_MAX_PAIRS = 1 << 34           # rows of A x rows of B one match call takes (131 072 x 131 072): the search is brute force
 SCORE_BATCH = 1 << 16               # hypotheses per nksr_pose_score launch (6 MB of transforms)
 assert SCORE_BATCH <= _lib.POSE_MAX_H
@@ -109,16 +108,8 @@ def fit_triples(src, tgt):
 
 
 # ---- argument checks ---------------------------------------------------------------------------------------------------------------------
-def _cloud(xyz, what):
-    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
-        raise RuntimeError('%s must be a floating-point [N,3] tensor' % what)
-    require_gpu(xyz.device)
-    return xyz.to(torch.float32).contiguous()
-
-
 def _unit_normals(normal, n, device):
-    if not torch.is_tensor(normal) or tuple(normal.shape) != (n, 3) or not normal.is_floating_point() or normal.device != device:
-        raise RuntimeError('normal must be a floating-point [%d, 3] tensor on the device of the cloud' % n)
+    cloud_input.rows_like(normal, n, device, None, 'normal', floating=True)
     m = normal.double()
     length = m.norm(dim=1, keepdim=True)
     if n and not (float(length.min()) > 0.0 and float(length.max()) < float('inf')):
@@ -132,13 +123,6 @@ def _features(f, what):
         raise RuntimeError('%s must be an FpfhFeature or a floating-point [N, %d] tensor' % (what, BINS))
     require_gpu(f.device)
     return f.to(torch.float32).contiguous()
-
-
-def _check_threshold(t, what):
-    t = float(t)
-    if not (0.0 < t < float('inf')):
-        raise ValueError('%s must be positive and finite (got %r)' % (what, t))
-    return t
 
 
 # ---- the kernels, one call each ------------------------------------------------------------------------------------------------------------
@@ -190,22 +174,19 @@ def pose_scores(src, tgt, transforms, threshold):
 def corr_sums(src, tgt, transform, centre, threshold):
     """``nksr_corr_accumulate`` + ``nksr_icp_reduce`` for ONE transform (float64 [3, 4] or [4, 4]) -> (mask uint8 [C] on the device, sums
     float64 numpy [NKSR_ICP_FIELDS], the point method's layout: one 256-byte read)."""
+    from .register import RowSums
     c, dev = src.shape[0], src.device
-    T = np.asarray(transform, np.float64)[:3].reshape(12)
-    args = torch.from_numpy(np.concatenate([T, np.asarray(centre, np.float64)])).to(dev)
-    nrows = (c + BLOCK - 1) // BLOCK
+    rows = RowSums(c, 12, dev)
+    rows.set(np.asarray(transform, np.float64)[:3], centre)
     mask = torch.empty(c, dtype=torch.uint8, device=dev)
-    partials = torch.empty((nrows, FIELDS), dtype=torch.float64, device=dev)
-    sums = torch.empty(FIELDS, dtype=torch.float64, device=dev)
-    call('nksr_corr_accumulate', ptr(src), ptr(tgt), c, args.data_ptr(), args.data_ptr() + 12 * 8, threshold, ptr(mask), ptr(partials), stream())
-    call('nksr_icp_reduce', ptr(partials), nrows, ptr(sums), stream())
-    return mask, sums.cpu().numpy()
+    call('nksr_corr_accumulate', ptr(src), ptr(tgt), c, rows.args_ptr, rows.centre_ptr, threshold, ptr(mask), ptr(rows.partials), stream())
+    return mask, rows.reduce()
 
 
 # ---- features ------------------------------------------------------------------------------------------------------------------------------
 def fpfh_on_index(index, normal, radius, max_nn=32):
     """``compute_fpfh_feature`` on a ``cloud.CloudIndex``."""
-    radius, max_nn = _check_threshold(radius, 'compute_fpfh_feature: radius'), int(max_nn)
+    radius, max_nn = cloud_input.positive(radius, 'compute_fpfh_feature', 'radius'), int(max_nn)
     if max_nn < 1 or max_nn > MAX_K:
         raise ValueError('compute_fpfh_feature: 1 <= max_nn <= %d (got %d)' % (MAX_K, max_nn))
     normal = _unit_normals(normal, index.n, index.device)
@@ -223,7 +204,7 @@ def compute_fpfh_feature(xyz, normal, radius, max_nn=32, index=None):
     meant.  ``index``: a ``CloudIndex`` of ``xyz`` built before."""
     from .cloud import CloudIndex
     if index is None:
-        index = CloudIndex(_cloud(xyz, 'xyz'))
+        index = CloudIndex(cloud_input.points(xyz, None))
     elif index.n != xyz.shape[0]:
         raise ValueError('compute_fpfh_feature: the index holds %d points, xyz %d' % (index.n, xyz.shape[0]))
     return fpfh_on_index(index, normal, radius, max_nn)
@@ -274,11 +255,11 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     from .register import evaluate_registration, kabsch_step
     if int(ransac_n) != 3:
         raise ValueError('registration_ransac_based_on_feature_matching: ransac_n must be 3 (got %r)' % (ransac_n,))
-    thr = _check_threshold(max_correspondence_distance, 'registration_ransac_based_on_feature_matching: max_correspondence_distance')
+    thr = cloud_input.positive(max_correspondence_distance, 'registration_ransac_based_on_feature_matching', 'max_correspondence_distance')
     max_iteration = int(max_iteration)
     if max_iteration < 1:
         raise ValueError('registration_ransac_based_on_feature_matching: max_iteration must be >= 1 (got %d)' % max_iteration)
-    source, target = _cloud(source, 'source'), _cloud(target, 'target')
+    source, target = cloud_input.points(source, None, 'source'), cloud_input.points(target, None, 'target')
     fs, ft = _features(source_feature, 'source_feature'), _features(target_feature, 'target_feature')
     if fs.shape[0] != source.shape[0] or ft.shape[0] != target.shape[0]:
         raise ValueError('registration_ransac_based_on_feature_matching: %d / %d features for %d / %d points' % (
@@ -330,10 +311,10 @@ def register_global(source, target, voxel_size, source_normal=None, target_norma
     (``ransac_kwargs`` go there); 4. with ``refine_icp``, ``icp(method='plane')`` on the FULL clouds at 1.5 ``voxel_size`` from that
     pose.  -> the result of the last stage (``IcpResult``, or ``RansacResult`` without ICP) with the RANSAC result as ``.ransac``."""
     from . import cloud
-    voxel_size = _check_threshold(voxel_size, 'register_global: voxel_size')
+    voxel_size = cloud_input.positive(voxel_size, 'register_global', 'voxel_size')
     clouds = []
     for xyz, normal, what in ((source, source_normal, 'source'), (target, target_normal, 'target')):
-        xyz = _cloud(xyz, what)
+        xyz = cloud_input.points(xyz, None, what)
         if normal is None:
             xyz, normal = cloud.estimate_normals(xyz, knn=32)
         down = cloud.voxel_downsample(xyz, voxel_size, normal=normal)

@@ -18,6 +18,7 @@ fp64 sums in a fixed order, no atomics: the same call gives the same bits.  GPU 
 import numpy as np
 import torch
 
+from . import cloud_input
 from ._lib import call, ptr, require_gpu, stream
 
 MIN_NEIGHBORS = {1: (3, 3), 2: (6, 8)}            # order -> (the floor: the unknowns of the fit, the default)
@@ -49,18 +50,14 @@ class MlsResult:
 
 def _check_args(what, radius, order, sigma, min_neighbors):
     """-> (radius as the fp32 value the kernel works with, sigma, order, min_neighbors); raises before anything touches a device"""
-    radius = float(radius)
-    if not (0.0 < radius < float('inf')):
-        raise ValueError('%s: radius must be positive and finite (got %r)' % (what, radius))
+    radius = cloud_input.positive(radius, what, 'radius')
     if order not in (1, 2) or isinstance(order, bool):
         raise ValueError('%s: order must be 1 or 2 (got %r)' % (what, order))
     order = int(order)
     h = float(np.float32(radius))
     if not (0.0 < h < float('inf')):
         raise ValueError('%s: radius must be positive and finite in float32 (got %r)' % (what, radius))
-    sigma = 0.5 * h if sigma is None else float(sigma)
-    if not (0.0 < sigma < float('inf')):
-        raise ValueError('%s: sigma must be positive and finite (got %r)' % (what, sigma))
+    sigma = cloud_input.positive(0.5 * h if sigma is None else sigma, what, 'sigma')
     floor, default = MIN_NEIGHBORS[order]
     m = default if min_neighbors is None else int(min_neighbors)
     if m < floor:
@@ -69,16 +66,9 @@ def _check_args(what, radius, order, sigma, min_neighbors):
 
 
 def _check_normal(what, normal, n):
-    if normal is None:
-        return
-    if not torch.is_tensor(normal) or normal.dim() != 2 or tuple(normal.shape) != (n, 3) or not normal.is_floating_point():
-        raise ValueError('%s: normal must be a floating-point [%d, 3] tensor, one row per point of the cloud (got %s)'
-                         % (what, n, tuple(normal.shape) if torch.is_tensor(normal) else type(normal).__name__))
-
-
-def _check_xyz(what, xyz):
-    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
-        raise RuntimeError('%s: xyz must be a floating-point [N,3] tensor' % what)
+    """shape and type alone (ValueError): the device is compared once the index is there"""
+    if normal is not None:
+        cloud_input.rows_like(normal, n, None, what, 'normal', floating=True, error=ValueError)
 
 
 def mls_on_index(index, radius, normal=None, query=None, order=2, sigma=None, min_neighbors=None):
@@ -93,9 +83,8 @@ def mls_on_index(index, radius, normal=None, query=None, order=2, sigma=None, mi
     g = index._radius_grid(float(radius))          # (the grid radius_count(radius) uses: cell = 1.02 radius >= fl32(radius))
     ns = None
     if normal is not None:
-        if normal.device != dev:
-            raise RuntimeError('mls_project: normal is on %s, the cloud on %s' % (normal.device, dev))
-        ns = normal.to(torch.float32)[g.perm].contiguous()
+        cloud_input.rows_like(normal, n, dev, 'mls_project', 'normal')
+        ns = g.to_grid(normal.to(torch.float32))
     if query is None:
         q, nq = None, n
     else:
@@ -110,7 +99,7 @@ def mls_on_index(index, radius, normal=None, query=None, order=2, sigma=None, mi
          ptr(gauss), ptr(var), ptr(count), ptr(used), stream())
     out = [pos, nrm, mean, gauss, var, count, used]
     if query is None:                       # grid order -> the caller's
-        out = [torch.empty_like(t).index_copy_(0, g.perm, t) for t in out]
+        out = [g.to_caller(t) for t in out]
     return MlsResult(*out)
 
 
@@ -121,7 +110,7 @@ def mls_project(xyz, radius, normal=None, query=None, order=2, sigma=None, min_n
     largest component of a normal is made positive); ``min_neighbors``: default 3 (order 1) / 8 (order 2), never below 3 / 6."""
     from .cloud import CloudIndex
     _check_args('mls_project', radius, order, sigma, min_neighbors)
-    _check_xyz('mls_project', xyz)
+    cloud_input.rows3(xyz, 'mls_project')
     _check_normal('mls_project', normal, xyz.shape[0])
     return mls_on_index(CloudIndex(xyz), radius, normal, query, order, sigma, min_neighbors)
 
@@ -135,7 +124,7 @@ def smooth_mls(xyz, radius, normal=None, iterations=1, order=2, sigma=None, min_
     _check_args('smooth_mls', radius, order, sigma, min_neighbors)
     if isinstance(iterations, bool) or int(iterations) != iterations or int(iterations) < 1:
         raise ValueError('smooth_mls: iterations must be an integer >= 1 (got %r)' % (iterations,))
-    _check_xyz('smooth_mls', xyz)
+    cloud_input.rows3(xyz, 'smooth_mls')
     _check_normal('smooth_mls', normal, xyz.shape[0])
     require_gpu(xyz.device)
     xyz = xyz.to(torch.float32)

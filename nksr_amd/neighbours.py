@@ -36,6 +36,16 @@ class PointGrid:
         self.end = torch.empty(self.grid.num_voxels, dtype=torch.int32, device=dev)
         call('nksr_site_ranges', ptr(ks), n, ptr(self.grid.keys), self.grid.num_voxels, 0, ptr(self.start), ptr(self.end), stream())
 
+    def to_grid(self, t):
+        """rows in the caller's order -> the grid's (Morton) order, contiguous"""
+        return t[self.perm].contiguous()
+
+    def to_caller(self, t):
+        """rows in the grid's order -> the caller's, in a fresh tensor"""
+        out = torch.empty_like(t)
+        out[self.perm] = t
+        return out
+
     def nearest(self, query, max_ring=8):
         """Index (into the ORIGINAL cloud order) of the nearest point of every query."""
         q = query.to(torch.float32).contiguous()

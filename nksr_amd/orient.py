@@ -20,8 +20,8 @@ import collections
 
 import torch
 
-from . import ops
-from ._lib import ORIENT_MAX_K, ORIENT_SEED_VIEWPOINT, ORIENT_SEED_Z, call, ptr, require_gpu, stream
+from . import cloud_input, ops
+from ._lib import ORIENT_MAX_K, ORIENT_SEED_VIEWPOINT, ORIENT_SEED_Z, call, ptr, stream
 
 OrientedNormals = collections.namedtuple('OrientedNormals', 'normal flipped component n_components')
 # normal float32 [N, 3]; flipped uint8 [N] (1: the input normal was negated); component int32 [N], dense ids in the order of every
@@ -52,13 +52,8 @@ def _check_k(k, n, what):
 
 def _check_cloud(xyz, normal, what):
     """float32 contiguous xyz / normal [N, 3] on one GPU, finite (one readback)"""
-    for name, a in (('xyz', xyz), ('normal', normal)):
-        if not torch.is_tensor(a) or a.dim() != 2 or a.shape[1] != 3 or not a.is_floating_point():
-            raise RuntimeError('%s: %s must be a floating-point [N,3] tensor' % (what, name))
-        require_gpu(a.device)
-    if normal.shape[0] != xyz.shape[0] or normal.device != xyz.device:
-        raise RuntimeError('%s: normal must be [N,3] on the device of xyz' % what)
-    xyz, normal = xyz.to(torch.float32).contiguous(), normal.to(torch.float32).contiguous()
+    xyz, normal = cloud_input.points(xyz, what), cloud_input.points(normal, what, 'normal')
+    cloud_input.rows_like(normal, xyz.shape[0], xyz.device, what, 'normal')
     if xyz.shape[0]:
         amax = torch.stack([xyz.abs().max(), normal.abs().max()]).tolist()
         if not amax[0] < float('inf'):
@@ -168,8 +163,7 @@ def _orient_on_index(index, normal, k, seed, viewpoint, stats=None):
     if k + 1 > index.n:
         raise ValueError('orient_normals: k = %d other points of a cloud of %d points' % (k, index.n))
     _seed_args(seed, viewpoint)                                             # (argument errors before the search)
-    if not torch.is_tensor(normal) or normal.shape != (index.n, 3):
-        raise RuntimeError('orient_normals: normal must be a floating-point [N,3] tensor')
+    cloud_input.rows_like(normal, index.n, None, 'orient_normals', 'normal')
     idx, _ = _timed(stats, 'knn', lambda: index.knn(k, exclude_self=True))
     return orient_graph(index.xyz, normal, idx.to(torch.int32), seed=seed, viewpoint=viewpoint, order=index.pg.perm, stats=stats)
 
@@ -197,13 +191,10 @@ def estimate_normals(xyz, knn=64, orient_k=16, seed='+z', viewpoint=None):
     from .normals import TooFewPoints, knn_pca
     knn, orient_k = int(knn), int(orient_k)
     _seed_args(seed, viewpoint)                                             # (argument errors first)
-    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
-        raise RuntimeError('estimate_normals: xyz must be a floating-point [N,3] tensor')
-    require_gpu(xyz.device)
+    xyz = cloud_input.points(xyz, 'estimate_normals')
     if knn < 3:
         raise ValueError('estimate_normals: knn must be at least 3 (got %d)' % knn)
     _check_k(orient_k, xyz.shape[0], 'estimate_normals')
-    xyz = xyz.to(torch.float32).contiguous()
     if xyz.shape[0] < max(knn, orient_k + 1):
         raise TooFewPoints('need at least knn=%d and orient_k + 1 = %d points' % (knn, orient_k + 1))
     pg, nrm, _, valid = knn_pca(xyz, knn)

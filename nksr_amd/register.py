@@ -18,8 +18,8 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, ops
-from ._lib import call, ptr, require_gpu, stream
+from . import _lib, cloud_input, ops
+from ._lib import call, ptr, stream
 
 FIELDS, BLOCK = _lib.ICP_FIELDS, _lib.ICP_BLOCK
 COUNT, D2 = _lib.ICP_COUNT, _lib.ICP_D2
@@ -152,16 +152,11 @@ def check_transformation(T, what='init'):
 
 
 def _check_source(source, device):
-    if not torch.is_tensor(source) or source.dim() != 2 or source.shape[1] != 3 or not source.is_floating_point():
-        raise RuntimeError('source must be a floating-point [N,3] tensor')
-    require_gpu(source.device)
+    source = cloud_input.points(source, None, 'source', finite=True)
     if source.device != device:
         raise RuntimeError('source is on %s, the target on %s' % (source.device, device))
     if source.shape[0] < 1:
         raise ValueError('icp: empty source')
-    source = source.to(torch.float32).contiguous()
-    if not float(source.abs().max()) < float('inf'):
-        raise RuntimeError('non-finite coordinates in the source')
     return source
 
 
@@ -174,13 +169,6 @@ def _target_index(target):
     return cloud.CloudIndex(target)
 
 
-def _check_radius(r):
-    r = float(r)
-    if not (0.0 < r < float('inf')):
-        raise ValueError('icp: max_correspondence_distance must be positive and finite (got %r)' % r)
-    return r
-
-
 def _check_method(method, target_normal, index):
     if method not in METHODS:
         raise ValueError("icp: method must be 'point' or 'plane' (got %r)" % (method,))
@@ -188,8 +176,7 @@ def _check_method(method, target_normal, index):
         return None
     if target_normal is None:
         raise ValueError("icp: method='plane' needs target_normal")
-    if not torch.is_tensor(target_normal) or tuple(target_normal.shape) != (index.n, 3) or target_normal.device != index.device:
-        raise RuntimeError('icp: target_normal must be a [%d, 3] tensor on the device of the target' % index.n)
+    cloud_input.rows_like(target_normal, index.n, index.device, 'icp', 'target_normal')
     return target_normal.to(torch.float32)
 
 
@@ -198,15 +185,13 @@ def apply_transform(xyz, transformation, normal=None):
     """``xyz`` [N, 3] moved by the 4 x 4 ``transformation``: fp64 arithmetic, rounded once to fp32.  With ``normal`` [N, 3] ->
     (xyz, normal): normals take the rotation only."""
     T = check_transformation(transformation, 'transformation')
-    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
-        raise RuntimeError('xyz must be a floating-point [N,3] tensor')
-    require_gpu(xyz.device)
+    cloud_input.rows3(xyz, None)
+    _lib.require_gpu(xyz.device)
     Td = torch.from_numpy(T).to(xyz.device)
     out = (xyz.double() @ Td[:3, :3].t() + Td[:3, 3]).float()
     if normal is None:
         return out
-    if not torch.is_tensor(normal) or normal.shape != xyz.shape or normal.device != xyz.device:
-        raise RuntimeError('normal must be a [N,3] tensor on the device of xyz')
+    cloud_input.rows_like(normal, xyz.shape[0], xyz.device, None, 'normal')
     return out, (normal.double() @ Td[:3, :3].t()).float()
 
 
@@ -219,6 +204,27 @@ def apply_transform(xyz, transformation, normal=None):
 SORT_SOURCE = True
 
 
+class RowSums:
+    """The device side of one pass of fixed-order sums over ``n`` items (``block_row_sums`` of csrc/icp_dev.h + ``nksr_icp_reduce``):
+    ``args`` = float64 [n_args + 3], the kernel's arguments followed by the centre the sums are taken about; ``partials`` = one row of
+    ``NKSR_ICP_FIELDS`` per workgroup of the accumulate kernel, which the owner launches between ``set`` and ``reduce``; ``sums``."""
+
+    def __init__(self, n, n_args, device):
+        self.nrows = (n + BLOCK - 1) // BLOCK
+        self.args = torch.empty(n_args + 3, dtype=torch.float64, device=device)
+        self.args_ptr, self.centre_ptr = self.args.data_ptr(), self.args.data_ptr() + 8 * n_args
+        self.partials = torch.empty((self.nrows, FIELDS), dtype=torch.float64, device=device)
+        self.sums = torch.empty(FIELDS, dtype=torch.float64, device=device)
+
+    def set(self, args, centre):
+        self.args.copy_(torch.from_numpy(np.concatenate([np.asarray(args, np.float64).reshape(-1), np.asarray(centre, np.float64)])))
+
+    def reduce(self):
+        """-> the sums as float64 numpy [NKSR_ICP_FIELDS]: the pass's one device-to-host read (256 bytes)"""
+        call('nksr_icp_reduce', ptr(self.partials), self.nrows, ptr(self.sums), stream())
+        return self.sums.cpu().numpy()
+
+
 class IcpPass:
     """Everything one (target, source, radius, method) needs on the device; ``run(T)`` -> the sums of the pass at ``T`` (float64 numpy,
     the pass's only device-to-host read)."""
@@ -227,7 +233,7 @@ class IcpPass:
         self.index, self.radius, self.method = index, radius, METHODS[method]
         dev = index.device
         g = self.grid = index._radius_grid(radius)
-        self.normal = target_normal[g.perm].contiguous() if target_normal is not None else None
+        self.normal = g.to_grid(target_normal) if target_normal is not None else None
         self.centre = index.bbox_centre()
         n = self.n = source.shape[0]
         self.order = None
@@ -240,23 +246,16 @@ class IcpPass:
             self.order = order.long()
             source = source[self.order].contiguous()
         self.source = source
-        self.nrows = (n + BLOCK - 1) // BLOCK
-        self.pose = torch.empty(15, dtype=torch.float64, device=dev)           # transform [12] + centre [3]
+        self.rows = RowSums(n, 12, dev)                                        # the transform's 12
         self.corr = torch.empty(n, dtype=torch.int64, device=dev)
-        self.partials = torch.empty((self.nrows, FIELDS), dtype=torch.float64, device=dev)
-        self.sums = torch.empty(FIELDS, dtype=torch.float64, device=dev)
-
-    def launch(self, T):
-        from .neighbours import _grid_args
-        g = self.grid
-        self.pose.copy_(torch.from_numpy(np.concatenate([T[:3].reshape(12), self.centre])))
-        call('nksr_icp_accumulate', ptr(g.xyz), self.index.n, *_grid_args(g), ptr(g.perm), ptr(self.normal), ptr(self.source), self.n,
-             self.pose.data_ptr(), self.pose.data_ptr() + 12 * 8, self.radius, self.method, ptr(self.corr), ptr(self.partials), stream())
-        call('nksr_icp_reduce', ptr(self.partials), self.nrows, ptr(self.sums), stream())
 
     def run(self, T):
-        self.launch(T)
-        return self.sums.cpu().numpy()
+        from .neighbours import _grid_args
+        g, rows = self.grid, self.rows
+        rows.set(T[:3], self.centre)
+        call('nksr_icp_accumulate', ptr(g.xyz), self.index.n, *_grid_args(g), ptr(g.perm), ptr(self.normal), ptr(self.source), self.n,
+             rows.args_ptr, rows.centre_ptr, self.radius, self.method, ptr(self.corr), ptr(rows.partials), stream())
+        return rows.reduce()
 
     def correspondences(self):
         """of the last pass, in the caller's source order"""
@@ -270,7 +269,7 @@ class IcpPass:
 def _prepare(source, target, max_correspondence_distance, init, method, target_normal, what):
     index = _target_index(target)
     source = _check_source(source, index.device)
-    radius = _check_radius(max_correspondence_distance)
+    radius = cloud_input.positive(max_correspondence_distance, 'icp', 'max_correspondence_distance')
     normal = _check_method(method, target_normal, index)
     T = check_transformation(init, what)
     return IcpPass(index, source, radius, method, normal, T), T

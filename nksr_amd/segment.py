@@ -10,18 +10,20 @@ out, and what is left split into its objects, so that small dense blobs and stra
     (``k_dbscan_border``) or is noise (-1); labels ascend with the smallest caller index among each cluster's core points.  Integers
     only.  Sizes and centroids: ``cloud.voxel_reduce`` over the points sorted by label (fp64 sums in a fixed order).
   * ``segment_plane``: RANSAC.  Hypotheses from point triples on the host (``sample_planes``: one gather of 3 H points read back),
-    scored in one launch (``plane_scores``: ``k_plane_score``, integer counts), the best refined by the principal axes of its inliers
-    (``k_plane_moments`` + ``nksr_icp_reduce``: fp64 sums in a fixed order; covariance and ``numpy.linalg.eigh`` on the host).
+    scored in one launch (``plane_scores``: ``k_hypothesis_score`` of csrc/score_dev.h, integer counts), the best refined by the
+    principal axes of its inliers (``k_plane_moments`` + ``nksr_icp_reduce``: fp64 sums in a fixed order; covariance and
+    ``numpy.linalg.eigh`` on the host).
 No floating-point atomics anywhere: the same call gives the same bits.  GPU tensors only.
 """
 import numpy as np
 import torch
 
-from . import _lib, ops
-from ._lib import call, ptr, require_gpu, stream
+from . import _lib, cloud_input, ops
+from ._lib import call, ptr, stream
 
-FIELDS, BLOCK = _lib.ICP_FIELDS, _lib.ICP_BLOCK
+FIELDS = _lib.ICP_FIELDS
 P_COUNT, P_SUM, P_MOMENT = _lib.PLANE_COUNT, _lib.PLANE_SUM, _lib.PLANE_MOMENT
+MAX_POINTS = (1 << 31) - 1          # what the plane kernels index
 DEGENERATE_NORMAL = 1e-12           # a triple whose (p1 - p0) x (p2 - p0) is no longer than this gives no plane
 
 
@@ -59,9 +61,7 @@ class DbscanResult:
 
 
 def _check_dbscan(eps, min_points):
-    eps, m = float(eps), int(min_points)
-    if not (0.0 < eps < float('inf')):
-        raise ValueError('cluster_dbscan: eps must be positive and finite (got %r)' % eps)
+    eps, m = cloud_input.positive(eps, 'cluster_dbscan', 'eps'), int(min_points)
     if m < 1:
         raise ValueError('cluster_dbscan: min_points must be >= 1 (got %r)' % (min_points,))
     return eps, m
@@ -113,10 +113,7 @@ def dbscan_on_index(index, eps, min_points):
     label = torch.empty(n, dtype=torch.int32, device=dev)
     call('nksr_uf_labels', ptr(parent), n, ptr(rank), ptr(label), stream())
     call('nksr_dbscan_border', ptr(g.xyz), n, *_grid_args(g), eps, ptr(core), ptr(label), stream())
-    labels = torch.empty(n, dtype=torch.int64, device=dev)
-    labels[g.perm] = label.long()
-    core_out = torch.empty(n, dtype=torch.bool, device=dev)
-    core_out[g.perm] = core.bool()
+    labels, core_out = g.to_caller(label.long()), g.to_caller(core.bool())
     sizes, centroid = cluster_stats(index.xyz, labels, nc)
     return DbscanResult(labels, core_out, nc, sizes, centroid)
 
@@ -133,15 +130,6 @@ def cluster_dbscan(xyz, eps, min_points):
 
 
 # ---- B. plane RANSAC -------------------------------------------------------------------------------------------------------------------
-def _check_cloud(xyz, what):
-    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
-        raise RuntimeError('%s: xyz must be a floating-point [N,3] tensor' % what)
-    require_gpu(xyz.device)
-    if xyz.shape[0] >= 1 << 31:
-        raise ValueError('%s: %d points, at most 2^31 - 1' % (what, xyz.shape[0]))
-    return xyz.to(torch.float32).contiguous()
-
-
 def _check_threshold(t, what):
     t = float(t)
     if not (0.0 <= t < float('inf')):
@@ -154,7 +142,7 @@ def sample_planes(xyz, num_iterations, seed=0):
     ``numpy.random.RandomState(seed).randint(0, N, (H, 3))``; their 3 H points are gathered on the device and read back once; in fp64
     numpy n = (p1 - p0) x (p2 - p0), scaled to unit length, d = -n . p0.  A triple with |n| <= 1e-12 before scaling is degenerate: its
     row is all zeros, and it scores -1."""
-    xyz = _check_cloud(xyz, 'sample_planes')
+    xyz = cloud_input.points(xyz, 'sample_planes', max_rows=MAX_POINTS)
     h, n = int(num_iterations), xyz.shape[0]
     if h < 1:
         raise ValueError('sample_planes: num_iterations must be >= 1 (got %r)' % (num_iterations,))
@@ -179,7 +167,7 @@ def planes_of_triples(p):
 def plane_scores(xyz, planes, distance_threshold):
     """int32 [H] on the device: the number of points of ``xyz`` with |((a x + b y) + c z) + d| <= ``distance_threshold`` (fp64, no
     fused multiply-add) for every row (a, b, c, d) of ``planes`` (float64 [H, 4], numpy or tensor); -1 for a degenerate row."""
-    xyz = _check_cloud(xyz, 'plane_scores')
+    xyz = cloud_input.points(xyz, 'plane_scores', max_rows=MAX_POINTS)
     t = _check_threshold(distance_threshold, 'plane_scores')
     pl = torch.as_tensor(planes, dtype=torch.float64)
     if pl.dim() != 2 or pl.shape[1] != 4:
@@ -220,23 +208,17 @@ class PlanePass:
     """``run(plane)`` -> (mask uint8 [N] on the device, sums float64 numpy [NKSR_ICP_FIELDS]: one 256-byte read) for one cloud."""
 
     def __init__(self, xyz, threshold):
-        from .density import bbox_center
+        from .register import RowSums
         self.xyz, self.t, self.n = xyz, threshold, xyz.shape[0]
-        dev = xyz.device
-        lo, hi, _ = bbox_center(xyz)
-        self.centre = 0.5 * (lo.double() + hi.double()).cpu().numpy()
-        self.nrows = (self.n + BLOCK - 1) // BLOCK
-        self.args = torch.empty(7, dtype=torch.float64, device=dev)          # plane [4] + centre [3]
-        self.partials = torch.empty((self.nrows, FIELDS), dtype=torch.float64, device=dev)
-        self.sums = torch.empty(FIELDS, dtype=torch.float64, device=dev)
+        self.centre = cloud_input.bbox_centre64(xyz)
+        self.rows = RowSums(self.n, 4, xyz.device)                            # the plane's 4
 
     def run(self, plane):
-        self.args.copy_(torch.from_numpy(np.concatenate([plane, self.centre])))
+        rows = self.rows
+        rows.set(plane, self.centre)
         mask = torch.empty(self.n, dtype=torch.uint8, device=self.xyz.device)
-        call('nksr_plane_moments', ptr(self.xyz), self.n, self.args.data_ptr(), self.args.data_ptr() + 4 * 8, self.t, ptr(mask),
-             ptr(self.partials), stream())
-        call('nksr_icp_reduce', ptr(self.partials), self.nrows, ptr(self.sums), stream())
-        return mask, self.sums.cpu().numpy()
+        call('nksr_plane_moments', ptr(self.xyz), self.n, rows.args_ptr, rows.centre_ptr, self.t, ptr(mask), ptr(rows.partials), stream())
+        return mask, rows.reduce()
 
 
 def segment_plane(xyz, distance_threshold, ransac_n=3, num_iterations=1000, seed=0):
@@ -247,12 +229,11 @@ def segment_plane(xyz, distance_threshold, ransac_n=3, num_iterations=1000, seed
     ``distance_threshold`` of the REFINED plane."""
     if int(ransac_n) != 3:
         raise ValueError('segment_plane: ransac_n must be 3 (got %r)' % (ransac_n,))
-    xyz = _check_cloud(xyz, 'segment_plane')
+    xyz = cloud_input.points(xyz, 'segment_plane', max_rows=MAX_POINTS)
     t = _check_threshold(distance_threshold, 'segment_plane')
     if xyz.shape[0] < 3:
         raise ValueError('segment_plane: a plane needs at least 3 points (got %d)' % xyz.shape[0])
-    if not float(xyz.abs().max()) < float('inf'):
-        raise RuntimeError('non-finite coordinates in the input')
+    cloud_input.all_finite(xyz, 'segment_plane')
     planes, _ = sample_planes(xyz, num_iterations, seed)
     counts = plane_scores(xyz, planes, t).cpu().numpy()
     best = int(np.argmax(counts))                       # (the first of the maxima: the lowest iteration)

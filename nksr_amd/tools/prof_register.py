@@ -154,15 +154,16 @@ def main():
 
             def acc(p):
                 call('nksr_icp_accumulate', ptr(g.xyz), index.n, *_grid_args(g), ptr(g.perm), ptr(p.normal), ptr(p.source), p.n,
-                     p.pose.data_ptr(), p.pose.data_ptr() + 96, radius, p.method, ptr(p.corr), ptr(p.partials), stream())
+                     p.rows.args_ptr, p.rows.centre_ptr, radius, p.method, ptr(p.corr), ptr(p.rows.partials), stream())
             for p in ps.values():
-                p.launch(T)
+                p.run(T)
+            rows = ps[True].rows
             ev = _events({'accumulate_sorted': lambda: acc(ps[True]), 'accumulate_caller': lambda: acc(ps[False]),
-                          'reduce': lambda: call('nksr_icp_reduce', ptr(ps[True].partials), ps[True].nrows, ptr(ps[True].sums), stream())},
+                          'reduce': lambda: call('nksr_icp_reduce', ptr(rows.partials), rows.nrows, ptr(rows.sums), stream())},
                          args.reps)
             out.update(ev)
             step = register.STEPS[method]
-            out['host_step'] = _clock(lambda: step(ps[True].sums.cpu().numpy(), ps[True].centre), args.reps)
+            out['host_step'] = _clock(lambda: step(rows.sums.cpu().numpy(), ps[True].centre), args.reps)
             out['pass'] = _clock(lambda: ps[True].run(T), args.reps)
             sums = ps[True].run(T)
             info = {'n_source': ps[True].n, 'n_target': index.n, 'cell': g.cell, 'fitness': float(sums[register.COUNT]) / ps[True].n,

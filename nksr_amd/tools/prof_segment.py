@@ -158,8 +158,8 @@ def main():
     mask = torch.empty(n, dtype=torch.uint8, device=dev)
     out.update(_events({
         'score': lambda: call('nksr_plane_score', ptr(xyz), n, ptr(pl), h, t, ptr(counts), stream()),
-        'moments': lambda: call('nksr_plane_moments', ptr(xyz), n, ps.args.data_ptr(), ps.args.data_ptr() + 32, t, ptr(mask), ptr(ps.partials), stream()),
-        'reduce': lambda: call('nksr_icp_reduce', ptr(ps.partials), ps.nrows, ptr(ps.sums), stream()),
+        'moments': lambda: call('nksr_plane_moments', ptr(xyz), n, ps.rows.args_ptr, ps.rows.centre_ptr, t, ptr(mask), ptr(ps.rows.partials), stream()),
+        'reduce': lambda: call('nksr_icp_reduce', ptr(ps.rows.partials), ps.rows.nrows, ptr(ps.rows.sums), stream()),
     }, args.reps))
     out['total'] = _clock(lambda: segment.segment_plane(xyz, t, num_iterations=h, seed=0), args.reps)
     got = counts.cpu().numpy()

@@ -229,6 +229,26 @@ def test_pose_scores_equal_a_numpy_count(h, c):
     assert want.max() > 0 or c == 3
 
 
+@pytest.mark.parametrize('h', [1, 63, 64, 65])
+@pytest.mark.parametrize('c', [0, 1, 511, 512, 513])
+def test_pose_scores_at_the_edges_of_the_scorer(c, h):
+    """No pair, one, and one less / exactly / one more than the 2 x 256 a workgroup holds, against one transform, one less / exactly /
+    one more than the 64 a workgroup stages: exact counts.  A NaN transform first, last and -- h = 65 -- alone in the last chunk: -1."""
+    from nksr_amd import global_register as gr
+    src, tgt, poses = _pairs_and_poses(c, h, 1000 * h + c)
+    bad = sorted({0, h - 1})
+    poses[bad] = np.nan
+    t = 0.05
+    good = np.setdiff1d(np.arange(h), bad)
+    t64 = tgt.astype(np.float64)
+    gap = min([np.abs(np.linalg.norm(register_ref.transform(poses[k], src) - t64, axis=1) - t).min() for k in good if c], default=1.0)
+    assert gap > 1e-9                                       # no count hangs on the last bits of a distance
+    want = fr.pose_counts(src, tgt, poses, t)
+    got = gr.pose_scores(_gpu(src), _gpu(tgt), poses, t).cpu().numpy()
+    assert np.array_equal(got, want)
+    assert (want[bad] == -1).all() and (want[good] >= 0).all() and (c < 511 or h < 63 or want.max() > 0)
+
+
 def test_pose_scores_of_transforms_that_are_not_finite_and_of_none():
     from nksr_amd import global_register as gr
     src, tgt, poses = _pairs_and_poses(700, 70, 9)

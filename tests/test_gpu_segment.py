@@ -1,4 +1,4 @@
-"""nksr_amd/segment.py on the GPU (csrc/segment.hip: k_dbscan_hook, k_dbscan_min_caller, k_dbscan_border, k_plane_score,
+"""nksr_amd/segment.py on the GPU (csrc/segment.hip: k_dbscan_hook, k_dbscan_min_caller, k_dbscan_border, k_hypothesis_score,
 k_plane_moments) against tests/segment_ref.py.
 
 Every integer result is compared index for index, nothing is left out.  Where a real-valued input could put a pair or a point on the
@@ -205,7 +205,29 @@ def test_plane_scores_count_every_point_of_a_small_cloud(n):
         assert want[-1] == -1 and (t < 2.0 ** -11 or want[-3] == n)
 
 
-# ---- 6. segment_plane end to end ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('h', [1, 127, 128, 129])
+@pytest.mark.parametrize('n', [0, 1, 1023, 1024, 1025])
+def test_plane_scores_at_the_edges_of_the_scorer(n, h):
+    """No point, one, and one less / exactly / one more than the 4 x 256 a workgroup holds, against one plane, one less / exactly / one
+    more than the 128 a workgroup stages: exact counts.  A degenerate plane first, last and -- h = 129 -- alone in the last chunk: -1."""
+    from nksr_amd import cloud
+    rs = np.random.RandomState(1000 * h + n)
+    xyz = rs.uniform(-1.0, 1.0, (n, 3)).astype(np.float32)
+    normal = rs.normal(size=(h, 3))
+    planes = np.concatenate([normal / np.linalg.norm(normal, axis=1, keepdims=True), rs.uniform(-0.3, 0.3, (h, 1))], axis=1)
+    bad = sorted({0, h - 1})
+    planes[bad] = 0.0
+    t = 0.1
+    good = np.setdiff1d(np.arange(h), bad)
+    gap = min([np.abs(np.abs(S.residuals(xyz, planes[k])) - t).min() for k in good if n], default=1.0)
+    assert gap > 1e-9                                       # no count hangs on the last bits of a residual
+    want = S.plane_counts(xyz, planes, t)
+    got = cloud.plane_scores(_gpu(xyz), planes, t).cpu().numpy()
+    assert np.array_equal(got, want)
+    assert (want[bad] == -1).all() and (want[good] >= 0).all() and (n < 1023 or h < 127 or want.max() > 0)
+
+
+# ---- 6. segment_plane end to end----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('h,seed', [(64, 0), (256, 1), (1000, 0)])
 def test_segment_plane_end_to_end(h, seed):
     from nksr_amd import cloud

@@ -236,6 +236,11 @@ def test_c_entry_point_rejects_bad_arguments_before_any_launch():
     assert call(grid=None) != 0 and 'NULL' in err()
     assert call(hcap=12) != 0 and 'hcap' in err()
     assert call(cell=0.05) != 0 and 'cell' in err()
+    # the words of the check that every radius search on a grid shares (csrc/knn_dev.h radius_grid_args)
+    for r in (0.0, -1.0, float('inf'), float('nan')):
+        assert call(radius=r) != 0 and 'mls project: radius must be positive and finite' in err()
+    assert call(hcap=12) != 0 and 'power of two' in err()
+    assert call(cell=0.05) != 0 and 'must be >= radius' in err()
     assert call(nq=11) != 0 and 'n_ref' in err()
     assert call(nq=-1) != 0 and 'negative' in err()
     assert call(out=None) != 0 and 'NULL' in err()
