@@ -1187,6 +1187,60 @@ int nksr_clip_corner_keys(const int32_t* faces, const int32_t* labels, int64_t n
 /* faces_out [nf, 3]: row q = the three entries of corner_vertex [3 nf] (the new vertex of every corner) of face order[q] */
 int nksr_clip_group_faces(const int32_t* order, const int32_t* corner_vertex, int64_t nf, int32_t* faces_out, void* stream);
 
+/* ---- mesh rasterisation (nksr_amd/mesh_raster.py: MeshRasterizer; csrc/meshraster.hip) -----------------------
+ * A mesh rasterised along one coordinate axis onto a regular grid: x = coordinate axis_x, y = axis_y, z = the third one, all read in
+ * the caller's precision (v_float64) and widened to fp64 exactly.  Pixel (i, j) of the [nx, ny] grid (flat index i ny + j, nx ny <
+ * 2^31) has the centre (origin_x + (i + 0.5) pixel_size, origin_y + (j + 0.5) pixel_size), one rounded product and one rounded sum
+ * each.  The definition (coverage by the signs of three edge functions with an antisymmetric tie-break, the height and the attributes
+ * from the same three values) is DESIGN.md section 3.18, restated in numpy by tests/mesh_raster_ref.py.  Faces as in the topology
+ * section (int32 / int64); a face is VALID when its indices are inside [0, nv) and its nine coordinates are finite.  No atomics: every
+ * id is a scan plus a position, every write has one writer.  Sequence: nksr_raster_boxes, nksr_exclusive_sum_i64 of the counts (read
+ * the candidates), nksr_raster_test, nksr_raster_flag_counts, nksr_exclusive_sum_i64 (read the hits), nksr_raster_compact, a stable
+ * nksr_sort_pairs_u64_u32 of (pixel, hit position), nksr_run_counts_u64 / nksr_run_table_u64, nksr_raster_pixel_start,
+ * nksr_raster_reduce; then nksr_raster_sample and nksr_raster_horn on the rasters. */
+#define NKSR_RASTER_BLOCK 256
+/* face_valid_out [nf]; box_out [nf, 4] = (i0, i1, j0, j1), the pixels floor((min - origin) / pixel_size) - 1 .. floor((max - origin) /
+ * pixel_size) + 1 per axis clamped to the grid (conservative while pixel_size >= 2^-40 of the largest coordinate or origin magnitude),
+ * i1 < i0 when the face is invalid or off the grid; count_out [nf + 1] = the pixels of the box, then a 0 (the input of the scan) */
+int nksr_raster_boxes(const void* v, int v_float64, int64_t nv, const void* faces, int faces_int64, int64_t nf, int axis_x, int axis_y,
+                      double origin_x, double origin_y, double pixel_size, int64_t nx, int64_t ny, uint8_t* face_valid_out, int32_t* box_out,
+                      int64_t* count_out, void* stream);
+/* One lane per candidate c < n_candidates < 2^31: its face is the last f with cand_start[f] <= c (cand_start [nf + 1] = the scan of
+ * count_out), its pixel the (c - cand_start[f])-th of the face's box, j fastest.  flag_out [n_candidates] = 1 where the face covers the
+ * centre, height_out [n_candidates] = ((U z_a + V z_b) + W z_c) / det there and 0 elsewhere. */
+int nksr_raster_test(const void* v, int v_float64, int64_t nv, const void* faces, int faces_int64, int64_t nf, int axis_x, int axis_y,
+                     double origin_x, double origin_y, double pixel_size, int64_t nx, int64_t ny, const int32_t* box, const int64_t* cand_start,
+                     int64_t n_candidates, uint8_t* flag_out, double* height_out, void* stream);
+/* counts_out [B + 1], B = ceil(n_candidates / NKSR_RASTER_BLOCK): the set flags of every block of candidates, then a 0 */
+int nksr_raster_flag_counts(const uint8_t* flag, int64_t n_candidates, int64_t* counts_out, void* stream);
+/* The hits in candidate order (which is face order), block_start [B + 1] the scan of counts_out and n_hits its last entry:
+ * hit_pixel_out [n_hits] = i ny + j, hit_face_out [n_hits], hit_height_out [n_hits] */
+int nksr_raster_compact(const uint8_t* flag, const double* height, const int32_t* box, const int64_t* cand_start, int64_t nf, int64_t n_candidates,
+                        int64_t nx, int64_t ny, const int64_t* block_start, int64_t n_hits, uint64_t* hit_pixel_out, int32_t* hit_face_out,
+                        double* hit_height_out, void* stream);
+/* pixel_start_out [n_pixels + 1] = the hits on the pixels before p, from the run table (run_keys [n_runs] = the covered pixels
+ * ascending, run_start [n_runs + 1]) of the sorted pixel keys */
+int nksr_raster_pixel_start(const uint64_t* run_keys, const int32_t* run_start, int64_t n_runs, int64_t n_hits, int64_t n_pixels,
+                            int64_t* pixel_start_out, void* stream);
+/* One lane per run.  order [n_hits] = the hit of every sorted position (ascending face id within a pixel: the sort is stable).
+ * layer_face_out / layer_height_out [n_hits] = the hits in sorted order; per covered pixel count_out = the length of its run,
+ * height_out = the largest (bottom != 0: the smallest) height of the run, face_out = the lowest face id that attains it.  The pixels
+ * without a run are not written: the caller fills the rasters with NaN / -1 / 0 first. */
+int nksr_raster_reduce(const uint64_t* run_keys, const int32_t* run_start, int64_t n_runs, const int32_t* order, const int32_t* hit_face,
+                       const double* hit_height, int64_t n_hits, int bottom, int64_t n_pixels, int32_t* layer_face_out, double* layer_height_out,
+                       double* height_out, int32_t* face_out, int32_t* count_out, void* stream);
+/* attr_out [nx ny, channels] fp64 = ((U t_a + V t_b) + W t_c) / det per channel of attr [nv, channels] (fp32, or fp64 with
+ * attr_float64 != 0) at the centre of every pixel, U, V, W recomputed for the face face_map [nx ny] names; NaN where face_map < 0.
+ * One lane per (pixel, group of 4 channels). */
+int nksr_raster_sample(const void* v, int v_float64, int64_t nv, const void* faces, int faces_int64, int64_t nf, int axis_x, int axis_y,
+                       double origin_x, double origin_y, double pixel_size, int64_t nx, int64_t ny, const int32_t* face_map, const void* attr,
+                       int attr_float64, int64_t channels, double* attr_out, void* stream);
+/* Horn's differences of height [nx, ny]: gx = (((h[i+1,j-1] + 2 h[i+1,j]) + h[i+1,j+1]) - ((h[i-1,j-1] + 2 h[i-1,j]) + h[i-1,j+1])) /
+ * (8 pixel_size), gy the same along j, shade = max(0, (s_z - (s_x gx + s_y gy)) / sqrt((1 + gx gx) + gy gy)) for sun = (s_x, s_y, s_z);
+ * NaN on the rim and where one of the nine heights is not finite.  Every operation rounded on its own. */
+int nksr_raster_horn(const double* height, int64_t nx, int64_t ny, double pixel_size, const double* sun, double* gx_out, double* gy_out,
+                     double* shade_out, void* stream);
+
 /* ---- mesh boundary loops and hole filling (nksr_amd/mesh_boundary.py: MeshBoundary; csrc/meshbound.hip) ----
  * The boundary half-edges of the topology section's edge table ordered into loops, their measures, and the faces that close them; the
  * definition is DESIGN.md section 3.16, restated in numpy by tests/mesh_boundary_ref.py.  Faces, validity and the limits as in the

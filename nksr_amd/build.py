@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libnksr_hip.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'nksr_hip.h')     # the C ABI: a source of the library, and what _lib.py binds from
-SOURCES = ['prims.hip', 'hierarchy.hip', 'splat.hip', 'kfield.hip', 'rows.hip', 'evalf.hip', 'gram.hip', 'assemble.hip', 'packed_rows.hip', 'spmv.hip', 'cheb.hip', 'pcg.hip', 'fused_tables.hip', 'fused_sweep.hip', 'fused.hip', 'meshing.hip', 'nn.hip', 'knn_normals.hip', 'knn_sdf.hip', 'knn_query.hip', 'chunks.hip', 'metrics.hip', 'meshquery.hip', 'meshtopo.hip', 'meshgeom.hip', 'meshsimp.hip', 'meshslice.hip', 'meshclip.hip', 'meshbound.hip', 'cloud.hip', 'orient.hip', 'register.hip', 'segment.hip', 'fpfh.hip', 'global_register.hip', 'mls.hip']
+SOURCES = ['prims.hip', 'hierarchy.hip', 'splat.hip', 'kfield.hip', 'rows.hip', 'evalf.hip', 'gram.hip', 'assemble.hip', 'packed_rows.hip', 'spmv.hip', 'cheb.hip', 'pcg.hip', 'fused_tables.hip', 'fused_sweep.hip', 'fused.hip', 'meshing.hip', 'nn.hip', 'knn_normals.hip', 'knn_sdf.hip', 'knn_query.hip', 'chunks.hip', 'metrics.hip', 'meshquery.hip', 'meshtopo.hip', 'meshgeom.hip', 'meshsimp.hip', 'meshslice.hip', 'meshclip.hip', 'meshraster.hip', 'meshbound.hip', 'cloud.hip', 'orient.hip', 'register.hip', 'segment.hip', 'fpfh.hip', 'global_register.hip', 'mls.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result'] + os.environ.get('NKSR_EXTRA_HIPCC_FLAGS', '').split()
 

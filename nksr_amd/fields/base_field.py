@@ -87,6 +87,13 @@ class MeshingResult:
         from ..mesh_clip import MeshClipper
         return MeshClipper(self.v, self.f, self.c).tiles(tile_size, origin, axes)
 
+    def height_map(self, pixel_size, origin=None, shape=None, axes=(0, 1), surface='top'):
+        """``HeightMap`` of this mesh on a regular grid (``MeshRasterizer.height_map``, nksr_amd/mesh_raster.py): elevation, covering
+        face and layer count per pixel on the lattice origin + k pixel_size that ``tiles`` and ``contours`` cut at; ``sample()`` on it
+        resamples the colours ``c`` (an orthoimage), ``slope()`` and ``hillshade()`` derive from it."""
+        from ..mesh_raster import MeshRasterizer
+        return MeshRasterizer(self.v, self.f, self.c).height_map(pixel_size, origin, shape, axes, surface)
+
     def boundary_loops(self):
         """``BoundaryLoops`` of this mesh (``MeshBoundary.loops``, nksr_amd/mesh_boundary.py): the boundary edges ordered into loops
         with their edge counts, lengths, areas, centroids and boxes."""

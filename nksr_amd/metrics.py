@@ -25,6 +25,7 @@ from .mesh_geometry import MeshGeometry  # noqa: F401  (re-exported: nksr.metric
 from .mesh_simplify import MeshSimplifier  # noqa: F401  (re-exported: nksr.metrics.MeshSimplifier)
 from .mesh_boundary import MeshBoundary  # noqa: F401  (re-exported: nksr.metrics.MeshBoundary)
 from .mesh_clip import MeshClipper  # noqa: F401  (re-exported: nksr.metrics.MeshClipper)
+from .mesh_raster import MeshRasterizer  # noqa: F401  (re-exported: nksr.metrics.MeshRasterizer)
 from .mesh_slice import MeshSlicer  # noqa: F401  (re-exported: nksr.metrics.MeshSlicer)
 from .mesh_topology import MeshTopology  # noqa: F401  (re-exported: nksr.metrics.MeshTopology)
 from .neighbours import PointGrid, PointPyramid, choose_cell_size

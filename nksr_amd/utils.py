@@ -119,6 +119,27 @@ def write_obj_polylines(path, points, polyline_start, polyline_points, closed=No
                 out.write('l ' + ' '.join('%d' % i for i in (list(row) + [row[0]] if loop[k] else row)) + '\n')
 
 
+def write_ascii_grid(path, height, origin, pixel_size, nodata=-9999.0):
+    """ESRI ASCII grid (.asc) of a raster ``height`` [nx, ny] (``HeightMap.height`` of nksr_amd/mesh_raster.py, or any raster on its
+    grid): six header lines -- ncols = nx, nrows = ny, the low corner ``origin`` of pixel (0, 0), the cell size, the no-data value --
+    and ny text rows of nx values.  The first row written is the largest axes[1] index, so the file is north-up; NaN is written as
+    ``nodata``.  Values are written with 17 significant digits and read back as they were."""
+    h = np.asarray(height.detach().cpu() if torch.is_tensor(height) else height, np.float64)
+    if h.ndim != 2:
+        raise ValueError('write_ascii_grid: expected an [nx, ny] raster, got shape %s' % (h.shape,))
+    try:
+        ox, oy = (float(o) for o in origin)
+        p, nodata = float(pixel_size), float(nodata)
+    except (TypeError, ValueError):
+        raise ValueError('write_ascii_grid: expected a two-number origin, a pixel size and a no-data value')
+    if not (p > 0.0 and np.isfinite([ox, oy, p, nodata]).all()):
+        raise ValueError('write_ascii_grid: expected a finite origin and no-data value and a positive pixel size')
+    rows = np.where(np.isnan(h), nodata, h).T[::-1]             # [ny, nx], the largest j first
+    with open(path, 'w') as out:
+        out.write('ncols %d\nnrows %d\nxllcorner %.17g\nyllcorner %.17g\ncellsize %.17g\nNODATA_value %.17g\n' % (h.shape[0], h.shape[1], ox, oy, p, nodata))
+        out.write(''.join(' '.join('%.17g' % x for x in row) + '\n' for row in rows))
+
+
 def warning_on_low_memory(threshold_mb):
     if torch.cuda.is_available():
         free, _ = torch.cuda.mem_get_info()
